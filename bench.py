@@ -8,14 +8,18 @@
 
 A step = Solver.train_step on one pre-staged synthetic batch: forward (STFT -> encoder -> complex LSTM -> decoder ->
 mask -> iSTFT), SI-SNR loss, full backward, gradient all-reduce (N>1), global-norm clip and Adam -- nothing skipped.
-Prints ONE JSON line (rank 0).  Also measured in the same run: the dominant kernel's roofline fraction (HIP events
-around repeated launches of that exact kernel on the launch stream) and the CPU baseline (the oracle's fp32 PyTorch
-restatement of the same step, timed on the host cores on a bounded sample).
+Every step starts from the seeded initial weights (one copy of them ahead of it), so it computes the same in every run.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and prints the line.  With --full the
+same run also measures: the dominant kernel's roofline fraction (HIP events around repeated launches of that exact
+kernel on the launch stream, PMC traffic from rocprofv3 child passes), the CPU baseline (the oracle's fp32 PyTorch
+restatement of the same step, timed on the host cores on a bounded sample) and the HIP-vs-oracle parity block.
+--dump-outputs DIR writes what the last timed step computed as .npy files (see dump_outputs).
 """
 import argparse
 import json
 import os
 import sys
+import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -52,7 +56,8 @@ def bench_config(length):
                   "load": False},
         "dset": {"name": "synthetic"},
         "solver": {"epochs": 1, "save_checkpoint_interval": 1000000, "all_steps": True, "total_steps": 0, "patience": 0,
-                   "root": "/tmp/sehip_bench", "resume": None, "preloaded_model": None, "log_interval": 1000000,
+                   "root": os.path.join(tempfile.gettempdir(), f"sehip_bench_{os.getuid()}"), "resume": None,
+                   "preloaded_model": None, "log_interval": 1000000,
                    "validation": {"interval": 1000000, "metric": "loss", "total_steps": 0}, "test": {"interval": 1000000}},
     })
 
@@ -597,6 +602,35 @@ def note(msg):
         print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_SAMPLE = 4 * 1024 * 1024       # entries: a longer flat vector is dumped as a fixed, seeded sample of this many
+
+
+def dump_outputs(path, loss, metric, model):
+    """--dump-outputs DIR: what the timed path (Solver.train_step) computed in its last step, as float32 .npy files: `loss` and
+    `grad_metric`, the pair the step returns, `grads` (the step's gradients), and the state it leaves behind -- `params` (after the
+    optimizer update) and `running_stats` (the normalisation layers' running statistics, where the network has any), each the model's
+    flat vector in its parameter layout.  A vector longer than DUMP_SAMPLE entries (Demucs: 133.7 M parameters) is written at
+    DUMP_SAMPLE positions drawn by a generator seeded with 0 and sorted: the same positions in every run of a network.  At most
+    3 x 16 MB.  Batch and weights come from fixed seeds and every step starts from the same weights (main()), so two runs, or two
+    builds, can be compared file by file; the default schedule's fp32 atomic sums still add in an order that varies from run to run."""
+    import numpy as np
+    arrays = {"loss": loss, "grad_metric": metric, "grads": model.flat_grads, "params": model.flat_params}
+    if model.static.layout.n_buffers:
+        arrays["running_stats"] = model._bflat
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randint(t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t[idx.to(t.device)]
+        a = t.float().cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        total += a.nbytes
+    assert total <= 64 * 1024 * 1024, total
+    note(f"outputs of the last timed step in {path}: {', '.join(arrays)} ({total / 1e6:.1f} MB)")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -613,6 +647,12 @@ def main():
                     "line's config.workload names the widths")
     ap.add_argument("--rnn-units", type=int, default=128, help="DCCRN only: 256 = the complex LSTM of the DCCRN paper (hidden 128 per "
                     "nn.LSTM; one launch per layer and direction).  A side measurement like --kernel-num")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: the per-kernel "
+                    "roofline pass (roofline, roofline_hbm, step_tflops, kernel_classes; PMC traffic from two rocprofv3 child passes), "
+                    "the CPU baseline of the oracle and the HIP-vs-oracle parity block (its HIP train steps run on the freshly "
+                    "initialised model, before the warm-up; the rest after the timed steps).  Each can be left out with its --no-* option")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="after the timed steps, write what the last one computed to "
+                    "DIR/<name>.npy (float32, at most 48 MB in all; see dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--graph", action="store_true", help="replay the step as two captured hipGraphs instead of launching "
@@ -629,6 +669,10 @@ def main():
                          "box torch's CPU ops with 256 threads did not finish ONE B=32 step in 15 minutes, 32 threads take ~5 s)")
     ap.add_argument("--cpu-baseline-worker", nargs=2, metavar=("STATE", "OUT"))
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        args.no_cpu_baseline = args.no_roofline = args.no_traffic = args.no_parity = True
     if args.kernel_num:
         widths = [int(v) for v in args.kernel_num.split(",")]
         if args.workload != "dccrn" or len(widths) != 6:
@@ -681,6 +725,11 @@ def main():
     else:
         noisy, clean = make_batch(args.batch, n, rank, dev)
     mixture, sources = solver._prepare_batch(noisy, clean)
+    # Every warm-up and timed step starts from these (seeded) weights: the same work as a training step, and what it computes is the
+    # same in every run.  Chained Adam steps on the one batch would carry the order noise of the default schedule's fp32 atomic sums
+    # forward: DCCRN, two runs, one step 2e-4 apart (gradients), 30 steps 4e-3 (parameters), 110 steps 3e-2.  The deterministic
+    # schedule (solver.cudnn_deterministic) is bit-exact but takes 1.8 x the step time.
+    params0 = model.flat_params.detach().clone()
     if dcu:
         # the reference transforms mixture and sources inside every step (src/solver.py:454-458): timed with the step
         base_step = (lambda fn: (lambda mix_, src_: fn(*solver._prepare_batch(noisy, clean))))
@@ -730,6 +779,7 @@ def main():
         copy_into(0)
 
     def one_step():
+        model.flat_params.copy_(params0)        # on the step's stream: the next forward packs its weights from them
         if args.h2d_overlap:
             i = state["k"] & 1
             state["k"] += 1
@@ -766,6 +816,9 @@ def main():
     note(f"{ms:.2f} ms/step")
     if dmx:
         model.workspace(args.batch, n).check_lstm_handoffs()    # the timed steps are valid only if no hand-off spin gave up
+    if args.dump_outputs and rank == 0:
+        # before anything else runs on the device: the roofline pass of --full re-launches the step's products into its buffers
+        dump_outputs(args.dump_outputs, loss, metric, model)
     value = world * args.batch * clip_s * args.steps / dt
 
     out = {

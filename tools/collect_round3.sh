@@ -12,12 +12,12 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/r3c
 mkdir -p $OUT
 cd $ROOT
-timeout 900 python bench.py 2>$OUT/bench.err | grep '^{' | tail -1 > $OUT/bench.json
+timeout 900 python bench.py --full 2>$OUT/bench.err | grep '^{' | tail -1 > $OUT/bench.json
 for w in dcunet convtasnet demucs; do
-  timeout 600 python bench.py --workload $w --steps 20 --warmup 3 2>$OUT/bench_$w.err | grep '^{' | tail -1 > $OUT/bench_$w.json
+  timeout 600 python bench.py --full --workload $w --steps 20 --warmup 3 2>$OUT/bench_$w.err | grep '^{' | tail -1 > $OUT/bench_$w.json
 done
 cd /tmp; export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- python3 $ROOT/bench.py --steps 30 --warmup 5 --no-cpu-baseline 2>/dev/null | grep '^{' | tail -1 > $OUT/bench_under_rocprof.json
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- python3 $ROOT/bench.py --full --steps 30 --warmup 5 --no-cpu-baseline 2>/dev/null | grep '^{' | tail -1 > $OUT/bench_under_rocprof.json
 SEHIP_NO_SIDE_STREAM=1 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_serial -o run -- python3 $ROOT/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-roofline > /dev/null 2>&1
 for w in dcunet convtasnet demucs; do
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$w -o run -- python3 $ROOT/bench.py --workload $w --steps 5 --warmup 2 --no-roofline --no-cpu-baseline > /dev/null 2>&1
