@@ -499,7 +499,7 @@ int sehip_dcunet_tail_bwd(const float* dout, const float* spec, float* mask_ws, 
                           float* gw_im, float* gb_im, float* bcoef, void* dy_bf16, float* gacc, void* stream);
 
 /* ---- ConvTasNet, everything that is not a 1x1 convolution (those are sehip_gemm products): src/model/conv_tasnet.py:34-487 with
- *      the shipped options (skip=False, gLN, non-causal, relu mask).  Activations are channels-last bf16 [M][K][C] (M utterances,
+ *      skip=False, relu mask (gLN, non-causal first; the causal and cLN entry points follow them).  Activations are channels-last bf16 [M][K][C] (M utterances,
  *      K = (T - L)/(L/2) + 1 frames); statistics records are double [M][2]; every accumulator named "caller zeroes" is added to
  *      with atomics.
  *      encoder_fwd : Conv1d(ac -> N, L, stride L/2, no bias) + ReLU (:157-176) and the cLN that follows (:439-462):
@@ -530,6 +530,32 @@ long sehip_ctn_gln_bwd_scratch_floats(int M, int K, int C);
 int sehip_ctn_gln_bwd(const void* g, const void* h, const float* slope, const double* stats, const float* gamma, const float* beta,
                       const float* Wd, int P, int dilation, int dw, int M, int K, int C, double* sums, float* gch, void* dh, float* dslope,
                       float* scratch, void* stream);
+/* causal=True (src/model/conv_tasnet.py:243, :405-419: padding (P - 1) d in front, nothing behind): the same two entry points with
+ * the taps at frames t - (P - 1 - j) d, j < P, instead of t + (j - P/2) d -- forward conv, transposed conv and dWd alike.
+ * (sehip_ctn_gln_bwd_causal with dw = 0 is sehip_ctn_gln_bwd.) */
+int sehip_ctn_dwconv_fwd_causal(const void* h1, const float* slope1, const double* stats1, const float* gamma, const float* beta,
+                                const float* Wd, int P, int dilation, const float* slope2, int M, int K, int C, void* h2, double* stats2,
+                                void* stream);
+int sehip_ctn_gln_bwd_causal(const void* g, const void* h, const float* slope, const double* stats, const float* gamma, const float* beta,
+                             const float* Wd, int P, int dilation, int dw, int M, int K, int C, double* sums, float* gch, void* dh,
+                             float* dslope, float* scratch, void* stream);
+/* norm_type='cLN' (:422-461: mean and biased variance over the C channels of ONE frame, eps = 1e-8 inside the root) for both norms
+ * of a temporal block.  Every sum is per frame and stays inside the lanes that hold the frame: no statistics records, and the
+ * backward pass is ONE pass (csrc/tasnet_cln.hip).  causal != 0: taps as in the *_causal entry points above.
+ *      cln_apply      : u = cLN(PReLU(h))
+ *      cln_dwconv_fwd : h2 = depthwise dilated Conv1d(groups = C, P = 3, 5 or 7) of cLN(PReLU(h1)); the moments of every tap row
+ *                       are recomputed from the row
+ *      cln_bwd        : gradient of y = cLN(PReLU(h)) [dw = 1: behind the depthwise conv, g = d h2]: dh,
+ *                       gch += {dgamma [C], dbeta [C] [, dWd [C][P]]}, dslope += d PReLU slope (caller zeroes both)
+ * scratch: sehip_ctn_cln_bwd_scratch_floats(M, K, C) floats (one row of partial sums per workgroup; a column-sum launch adds them
+ * into gch / dslope: in row order under the deterministic schedule) */
+int sehip_ctn_cln_apply(const void* h, const float* slope, const float* gamma, const float* beta, int M, int K, int C, void* u, void* stream);
+int sehip_ctn_cln_dwconv_fwd(const void* h1, const float* slope1, const float* gamma, const float* beta, const float* Wd, int P,
+                             int dilation, int causal, int M, int K, int C, void* h2, void* stream);
+long sehip_ctn_cln_bwd_scratch_floats(int M, int K, int C);
+int sehip_ctn_cln_bwd(const void* g, const void* h, const float* slope, const float* gamma, const float* beta, const float* Wd, int P,
+                      int dilation, int dw, int causal, int M, int K, int C, float* gch, void* dh, float* dslope, float* scratch,
+                      void* stream);
 /* mask_nonlinear='softmax' (src/model/conv_tasnet.py:298-299: F.softmax(score, dim=1) over the Cs <= 8 sources): score / out bf16
  * [rows = M * K][Cs][N].  The decoder entry points below take `out` as their mask logits (their relu is the identity on it); what
  * sehip_ctn_decoder_bwd writes for it is the gradient of the mask, which sehip_ctn_mask_softmax_bwd turns into the gradient of the

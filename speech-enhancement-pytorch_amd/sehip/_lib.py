@@ -135,6 +135,12 @@ _PROTOS = {
     "sehip_ctn_gln_apply": [P, P, P, P, P, I, I, I, P, P],
     "sehip_ctn_gln_bwd": [P, P, P, P, P, P, P, I, I, I, I, I, I, P, P, P, P, P, P],
     "sehip_ctn_gln_bwd_scratch_floats": [I, I, I],
+    "sehip_ctn_dwconv_fwd_causal": [P, P, P, P, P, P, I, I, P, I, I, I, P, P, P],
+    "sehip_ctn_gln_bwd_causal": [P, P, P, P, P, P, P, I, I, I, I, I, I, P, P, P, P, P, P],
+    "sehip_ctn_cln_apply": [P, P, P, P, I, I, I, P, P],
+    "sehip_ctn_cln_dwconv_fwd": [P, P, P, P, P, I, I, I, I, I, I, P, P],
+    "sehip_ctn_cln_bwd_scratch_floats": [I, I, I],
+    "sehip_ctn_cln_bwd": [P, P, P, P, P, P, I, I, I, I, I, I, I, P, P, P, P, P],
     "sehip_ctn_mask_softmax_fwd": [P, L, I, I, P, P],
     "sehip_ctn_mask_softmax_bwd": [P, P, L, I, I, P],
     "sehip_ctn_decoder_fwd": [P, P, P, I, I, I, I, I, I, I, P, P],
@@ -165,7 +171,7 @@ _PROTOS = {
     "sehip_lstm_fwd_chunk": [P, P, P, I, I, I, I, I, P, P, P, P],
     "sehip_lstm_bwd_chunk": [P, P, P, P, P, I, I, I, I, I, P, P, P, P],
 }
-_RESTYPE = {"sehip_lstm2_gran_bytes": C.c_long, "sehip_dmx_attn_bwd_scratch_floats": C.c_long, "sehip_ctn_codec_bwd_scratch_floats": C.c_long, "sehip_ctn_gln_bwd_scratch_floats": C.c_long, "sehip_wgrad_group_bytes": C.c_long, "sehip_wgrad_dense_group_bytes": C.c_long, "sehip_cbn_scratch_floats": C.c_long, "sehip_rbn_scratch_floats": C.c_long, "sehip_dcunet_tail_scratch_floats": C.c_long, "sehip_event_create": C.c_void_p, "sehip_stream_create": C.c_void_p}
+_RESTYPE = {"sehip_lstm2_gran_bytes": C.c_long, "sehip_dmx_attn_bwd_scratch_floats": C.c_long, "sehip_ctn_codec_bwd_scratch_floats": C.c_long, "sehip_ctn_gln_bwd_scratch_floats": C.c_long, "sehip_ctn_cln_bwd_scratch_floats": C.c_long, "sehip_wgrad_group_bytes": C.c_long, "sehip_wgrad_dense_group_bytes": C.c_long, "sehip_cbn_scratch_floats": C.c_long, "sehip_rbn_scratch_floats": C.c_long, "sehip_dcunet_tail_scratch_floats": C.c_long, "sehip_event_create": C.c_void_p, "sehip_stream_create": C.c_void_p}
 
 
 def lib():

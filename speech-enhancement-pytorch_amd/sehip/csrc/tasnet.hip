@@ -17,33 +17,8 @@
 //         dv = (gamma dy - mean(gamma dy) - xh mean(gamma dy xh)) / sigma;  dh = dv (h > 0 ? 1 : a);  da = sum dv h [h <= 0]
 #include "common.h"
 #include "det.h"
+#include "ctn.h"
 
-#define CTN_EPS 1e-8f
-
-struct C8 { float v[8]; };
-__device__ __forceinline__ C8 ld8(const bf16_raw* p) {
-    const uint4 u = *reinterpret_cast<const uint4*>(p);
-    C8 c;
-    c.v[0] = bf2f((bf16_raw)(u.x & 0xffff)); c.v[1] = bf2f((bf16_raw)(u.x >> 16));
-    c.v[2] = bf2f((bf16_raw)(u.y & 0xffff)); c.v[3] = bf2f((bf16_raw)(u.y >> 16));
-    c.v[4] = bf2f((bf16_raw)(u.z & 0xffff)); c.v[5] = bf2f((bf16_raw)(u.z >> 16));
-    c.v[6] = bf2f((bf16_raw)(u.w & 0xffff)); c.v[7] = bf2f((bf16_raw)(u.w >> 16));
-    return c;
-}
-__device__ __forceinline__ void st8(bf16_raw* p, const float* v) {
-    *reinterpret_cast<uint4*>(p) = make_uint4(pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]), pack_bf2(v[4], v[5]), pack_bf2(v[6], v[7]));
-}
-__device__ __forceinline__ uint4 ld8raw(const bf16_raw* p) { return *reinterpret_cast<const uint4*>(p); }
-__device__ __forceinline__ C8 unpack8(const uint4 u) {
-    C8 c;
-    c.v[0] = bf2f((bf16_raw)(u.x & 0xffff)); c.v[1] = bf2f((bf16_raw)(u.x >> 16));
-    c.v[2] = bf2f((bf16_raw)(u.y & 0xffff)); c.v[3] = bf2f((bf16_raw)(u.y >> 16));
-    c.v[4] = bf2f((bf16_raw)(u.z & 0xffff)); c.v[5] = bf2f((bf16_raw)(u.z >> 16));
-    c.v[6] = bf2f((bf16_raw)(u.w & 0xffff)); c.v[7] = bf2f((bf16_raw)(u.w >> 16));
-    return c;
-}
-__device__ __forceinline__ C8 zero8() { C8 c; for (int j = 0; j < 8; ++j) c.v[j] = 0.f; return c; }
-__device__ __forceinline__ float prelu(float h, float a) { return h > 0.f ? h : a * h; }
 
 // mean and 1/sigma of an utterance from its (sum, sumsq) record
 __device__ __forceinline__ void gln_moments(const double* __restrict__ st, int m, long n, float& mu, float& rs) {
@@ -566,27 +541,10 @@ __global__ __launch_bounds__(256) void ctn_gln_stats_kernel(const bf16_raw* __re
     block_add2_double(s, q, stats + 2 * m, dc);
 }
 
-// Thread layout of the frame-streaming kernels below: a thread owns ONE piece of 8 channels (q = tid % nq) for all its
-// frames, so gamma / beta / the depthwise taps of those channels are loaded once and stay in registers (fetched per piece
-// they were 40 four-byte loads beside 3-8 sixteen-byte ones, and the kernels ran at the address unit's pace: 90-260 us for
-// 26-MB tensors); rows t = bx*rpb + tid/nq, stepping by gridDim.x*rpb (rpb = 256/nq rows per block pass).
-struct PieceMap { int q, c0, rsub, rpb; bool active; };
-__device__ __forceinline__ PieceMap piece_map(int nq) {
-    PieceMap p;
-    p.rpb = 256 / nq;
-    p.q = threadIdx.x % nq;
-    p.rsub = threadIdx.x / nq;
-    p.c0 = p.q * 8;
-    p.active = p.rsub < p.rpb;
-    return p;
-}
-__device__ __forceinline__ void ld8f(const float* __restrict__ p, float (&v)[8]) {
-    const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
 
 // h2[t][c] = sum_j Wd[c][j] n1[t + (j - P/2) d][c],  n1 = gLN1(PReLU(h1)) (zero outside [0, K)); stats2 += PReLU(h2; a2)
-template <int P>
+// CAUSAL: the taps reach back only, h2[t] = sum_j Wd[j] n1[t - (P - 1 - j) d] (padding (P - 1) d in front, :243, :405-419)
+template <int P, bool CAUSAL = false>
 __global__ __launch_bounds__(256) void ctn_dwconv_fwd_kernel(const bf16_raw* __restrict__ h1, const float* __restrict__ slope1,
                                                              const double* __restrict__ stats1, const float* __restrict__ gamma,
                                                              const float* __restrict__ beta, const float* __restrict__ Wd /*[C][P]*/,
@@ -616,7 +574,7 @@ __global__ __launch_bounds__(256) void ctn_dwconv_fwd_kernel(const bf16_raw* __r
             bool ok[P];
 #pragma unroll
             for (int p = 0; p < P; ++p) {
-                const int tt = t + (p - P / 2) * dil;
+                const int tt = t + (p - (CAUSAL ? P - 1 : P / 2)) * dil;
                 ok[p] = tt >= 0 && tt < K;
                 x[p] = ld8(base + (long)(ok[p] ? tt : t) * C);          // all loads in flight together (the centre row stands in)
             }
@@ -669,7 +627,8 @@ __global__ __launch_bounds__(256) void ctn_gln_apply_kernel(const bf16_raw* __re
 //                  flushed each block with fp32 atomics: 1 600 blocks x 1 280 addresses, 261 us for a 26-MB tensor.)
 // pass 2 (apply) : dh = ((gamma dy - S1/n - xh S2/n) / sigma) (h > 0 ? 1 : a);  dslope += sum dv h [h <= 0]
 // gch layout: dgamma [C] | dbeta [C] | dWd [C][P] (DW only)
-template <int P, bool DW>
+// CAUSAL (centre tap P - 1 instead of P/2): the rows of dh2 are t + p d, p = 0 .. P-1, again tap p' = P - 1 - p.
+template <int P, bool DW, bool CAUSAL = false>
 __global__ __launch_bounds__(256) void ctn_gln_bwd_reduce_kernel(const bf16_raw* __restrict__ g, const bf16_raw* __restrict__ h,
                                                                  const float* __restrict__ slope, const double* __restrict__ stats,
                                                                  const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -719,7 +678,7 @@ __global__ __launch_bounds__(256) void ctn_gln_bwd_reduce_kernel(const bf16_raw*
                 // (t - (p' - P/2) d, t) as sum_t dh2[t] n[t + (p' - P/2) d], indexed by the row that holds n
 #pragma unroll
                 for (int p = 0; p < P; ++p) {
-                    const int tt = t + (p - P / 2) * dil;
+                    const int tt = t + (p - (CAUSAL ? 0 : P / 2)) * dil;
                     r.gq[p] = ld8raw(gb + (long)((tt >= 0 && tt < K) ? tt : t) * C);
                 }
             }
@@ -737,7 +696,7 @@ __global__ __launch_bounds__(256) void ctn_gln_bwd_reduce_kernel(const bf16_raw*
                 dy = zero8();
 #pragma unroll
                 for (int p = 0; p < P; ++p) {
-                    const int tt = t + (p - P / 2) * dil;      // the row t + (p - P/2) d is t - (p' - P/2) d for tap p' = P - 1 - p
+                    const int tt = t + (p - (CAUSAL ? 0 : P / 2)) * dil;      // the row t + (p - P/2) d is t - (p' - P/2) d for tap p' = P - 1 - p
                     if (tt >= 0 && tt < K) {
                         const C8 gp = unpack8(r.gq[p]);
 #pragma unroll
@@ -842,7 +801,7 @@ __global__ __launch_bounds__(256) void ctn_colsum_kernel(const float* __restrict
     atomicAdd(&out[c], s);
 }
 
-template <int P, bool DW>
+template <int P, bool DW, bool CAUSAL = false>
 __global__ __launch_bounds__(256) void ctn_gln_bwd_apply_kernel(const bf16_raw* __restrict__ g, const bf16_raw* __restrict__ h,
                                                                 const float* __restrict__ slope, const double* __restrict__ stats,
                                                                 const float* __restrict__ gamma, const float* __restrict__ Wd, int dil,
@@ -914,7 +873,7 @@ __global__ __launch_bounds__(256) void ctn_gln_bwd_apply_kernel(const bf16_raw* 
                 bool ok[P];
 #pragma unroll
                 for (int p = 0; p < P; ++p) {
-                    const int tt = t - (p - P / 2) * dil;
+                    const int tt = t - (p - (CAUSAL ? P - 1 : P / 2)) * dil;
                     ok[p] = tt >= 0 && tt < K;
                     gq[p] = ld8(gb + (long)(ok[p] ? tt : t) * C);
                 }
@@ -1246,11 +1205,6 @@ __global__ __launch_bounds__(256) void ctn_decoder_bwd_reg_kernel(const float* _
 // ------------------------------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------------------------------
-static int ctn_check(const char* who, int M, int K, int C) {
-    SEHIP_REQUIRE(M > 0 && K > 0, "%s: empty input", who);
-    SEHIP_REQUIRE(C >= 8 && C <= 512 && (C & 7) == 0, "%s: channels C=%d must be a multiple of 8 in [8, 512]", who, C);
-    return 0;
-}
 // the backward reductions pay a per-workgroup prologue / epilogue (40 channel constants, the LDS image, a partial row):
 // ~512 workgroups in all, each thread then walks 10+ rows
 static dim3 ctn_reduce_grid(int M, int K, int C) {
@@ -1268,16 +1222,6 @@ static dim3 ctn_colsum_grid(int nrows, int ncols) {
     if (rs > 64) rs = 64;
     if (rs < 1 || sehip_deterministic()) rs = 1;       // deterministic schedule: one add per column, rows in row order
     return dim3((unsigned)((ncols + 255) / 256), (unsigned)rs);
-}
-static dim3 ctn_grid(int M, int K, int C) {
-    long pieces = (long)K * (C >> 3);
-    // 16-byte pieces per thread (C4 step, ms: 4: 3.82, 6: 3.77, 8: 3.78, 16: 3.82, 32: 4.16; 2: 5.6 -- every workgroup pays the
-    // per-channel constants and, in the backward apply pass, its share of the column sums)
-    static const int rows = getenv("SEHIP_CTN_ROWS") ? atoi(getenv("SEHIP_CTN_ROWS")) : 6;
-    long g = (pieces + 256 * rows - 1) / (256 * rows);
-    if (g < 1) g = 1;
-    if (g > 64) g = 64;
-    return dim3((unsigned)g, (unsigned)M);
 }
 
 extern "C" int sehip_ctn_encoder_fwd(const float* wav, const float* U, const float* gamma, const float* beta, int M, int ac, int T, int N,
@@ -1383,8 +1327,9 @@ extern "C" int sehip_ctn_gln_stats(const void* h, const float* slope, int M, int
     return 0;
 }
 
-extern "C" int sehip_ctn_dwconv_fwd(const void* h1, const float* slope1, const double* stats1, const float* gamma, const float* beta,
-                                    const float* Wd, int P, int dilation, const float* slope2, int M, int K, int C, void* h2, double* stats2,
+template <bool CAUSAL>
+static int ctn_dwconv_fwd_impl(const void* h1, const float* slope1, const double* stats1, const float* gamma, const float* beta,
+                              const float* Wd, int P, int dilation, const float* slope2, int M, int K, int C, void* h2, double* stats2,
                                     void* stream) {
     if (int e = ctn_check("ctn_dwconv_fwd", M, K, C)) return e;
     SEHIP_REQUIRE(P == 3 || P == 5 || P == 7, "ctn_dwconv_fwd: kernel size P must be 3, 5 or 7 (got %d)", P);
@@ -1392,7 +1337,7 @@ extern "C" int sehip_ctn_dwconv_fwd(const void* h1, const float* slope1, const d
     bool ok;
     const DetCtx dc = sehip_det_ctx((hipStream_t)stream, (size_t)grid.x * grid.y * 2, &ok);
     if (!ok) return -2;
-#define CTN_DWF(P_) ctn_dwconv_fwd_kernel<P_><<<grid, 256, 0, (hipStream_t)stream>>>((const bf16_raw*)h1, slope1, stats1, gamma, beta, Wd, dilation, \
+#define CTN_DWF(P_) ctn_dwconv_fwd_kernel<P_, CAUSAL><<<grid, 256, 0, (hipStream_t)stream>>>((const bf16_raw*)h1, slope1, stats1, gamma, beta, Wd, dilation, \
                                                                             slope2, K, C, (bf16_raw*)h2, stats2, dc)
     if (P == 3) CTN_DWF(3);
     else if (P == 5) CTN_DWF(5);
@@ -1401,6 +1346,18 @@ extern "C" int sehip_ctn_dwconv_fwd(const void* h1, const float* slope1, const d
     if (int e = sehip_det_finish((hipStream_t)stream, dc, (int)grid.y, (int)grid.x, 2, stats2, 2)) return e;
     SEHIP_CHECK_LAUNCH("ctn_dwconv_fwd");
     return 0;
+}
+
+extern "C" int sehip_ctn_dwconv_fwd(const void* h1, const float* slope1, const double* stats1, const float* gamma, const float* beta,
+                                    const float* Wd, int P, int dilation, const float* slope2, int M, int K, int C, void* h2, double* stats2,
+                                    void* stream) {
+    return ctn_dwconv_fwd_impl<false>(h1, slope1, stats1, gamma, beta, Wd, P, dilation, slope2, M, K, C, h2, stats2, stream);
+}
+// causal=True (src/model/conv_tasnet.py:243, :405-419): the same with the P taps at frames t - (P - 1 - j) d, zeros before frame 0
+extern "C" int sehip_ctn_dwconv_fwd_causal(const void* h1, const float* slope1, const double* stats1, const float* gamma, const float* beta,
+                                           const float* Wd, int P, int dilation, const float* slope2, int M, int K, int C, void* h2,
+                                           double* stats2, void* stream) {
+    return ctn_dwconv_fwd_impl<true>(h1, slope1, stats1, gamma, beta, Wd, P, dilation, slope2, M, K, C, h2, stats2, stream);
 }
 
 extern "C" int sehip_ctn_gln_apply(const void* h, const float* slope, const double* stats, const float* gamma, const float* beta, int M, int K,
@@ -1419,7 +1376,8 @@ extern "C" long sehip_ctn_gln_bwd_scratch_floats(int M, int K, int C) {
     return (long)grid.x * grid.y * (9L * C + 3);          // partial rows of 2 + P <= 9 values per channel + three slope-gradient sums per workgroup
 }
 
-extern "C" int sehip_ctn_gln_bwd(const void* g, const void* h, const float* slope, const double* stats, const float* gamma, const float* beta,
+template <bool CAUSAL>
+static int ctn_gln_bwd_impl(const void* g, const void* h, const float* slope, const double* stats, const float* gamma, const float* beta,
                                  const float* Wd, int P, int dilation, int dw, int M, int K, int C, double* sums, float* gch, void* dh,
                                  float* dslope, float* scratch, void* stream) {
     if (int e = ctn_check("ctn_gln_bwd", M, K, C)) return e;
@@ -1437,9 +1395,9 @@ extern "C" int sehip_ctn_gln_bwd(const void* g, const void* h, const float* slop
     if (dw) {
 #define CTN_GB(P_)                                                                                                                                                         \
     do {                                                                                                                                                                   \
-        ctn_gln_bwd_reduce_kernel<P_, true><<<rgrid, 256, lds, st>>>((const bf16_raw*)g, (const bf16_raw*)h, slope, stats, gamma, beta, Wd, dilation, K, C, sums, scratch, dc); \
+        ctn_gln_bwd_reduce_kernel<P_, true, CAUSAL><<<rgrid, 256, lds, st>>>((const bf16_raw*)g, (const bf16_raw*)h, slope, stats, gamma, beta, Wd, dilation, K, C, sums, scratch, dc); \
         if (int e = sehip_det_finish(st, dc, (int)rgrid.y, (int)rgrid.x, 2, sums, 2)) return e;                                                                            \
-        ctn_gln_bwd_apply_kernel<P_, true><<<grid, 256, 0, st>>>((const bf16_raw*)g, (const bf16_raw*)h, slope, stats, gamma, Wd, dilation, sums, K, C, (bf16_raw*)dh,      \
+        ctn_gln_bwd_apply_kernel<P_, true, CAUSAL><<<grid, 256, 0, st>>>((const bf16_raw*)g, (const bf16_raw*)h, slope, stats, gamma, Wd, dilation, sums, K, C, (bf16_raw*)dh,      \
                                                                  dslope, scratch, nrows, ncols, gch, det);                                                                  \
     } while (0)
         if (P == 3) CTN_GB(3);
@@ -1454,6 +1412,18 @@ extern "C" int sehip_ctn_gln_bwd(const void* g, const void* h, const float* slop
     }
     SEHIP_CHECK_LAUNCH("ctn_gln_bwd");
     return 0;
+}
+
+extern "C" int sehip_ctn_gln_bwd(const void* g, const void* h, const float* slope, const double* stats, const float* gamma, const float* beta,
+                                 const float* Wd, int P, int dilation, int dw, int M, int K, int C, double* sums, float* gch, void* dh,
+                                 float* dslope, float* scratch, void* stream) {
+    return ctn_gln_bwd_impl<false>(g, h, slope, stats, gamma, beta, Wd, P, dilation, dw, M, K, C, sums, gch, dh, dslope, scratch, stream);
+}
+// causal=True: the transposed depthwise conv and dWd of dw = 1 with the taps of sehip_ctn_dwconv_fwd_causal (dw = 0 is sehip_ctn_gln_bwd)
+extern "C" int sehip_ctn_gln_bwd_causal(const void* g, const void* h, const float* slope, const double* stats, const float* gamma,
+                                        const float* beta, const float* Wd, int P, int dilation, int dw, int M, int K, int C, double* sums,
+                                        float* gch, void* dh, float* dslope, float* scratch, void* stream) {
+    return ctn_gln_bwd_impl<true>(g, h, slope, stats, gamma, beta, Wd, P, dilation, dw, M, K, C, sums, gch, dh, dslope, scratch, stream);
 }
 
 // mask_nonlinear='softmax' (src/model/conv_tasnet.py:298-299: est_mask = F.softmax(score, dim=1), over the Cs sources): a pass of its own

@@ -3,8 +3,9 @@
 Same constructor arguments, same ``forward(mixture[M, ac, T]) -> [M, C, ac, T]`` (C = len(sources)), same state_dict keys
 (``encoder.conv1d_U.weight``, ``separator.network.{0,1,2.r.x.net...,3}``, ``decoder.basis_signals.weight``), so the
 reference's checkpoints load here and vice versa.  Parameters are views into one flat fp32 buffer; forward / backward run the
-HIP kernels through the C ABI; a CPU tensor raises SehipError.  Built: the shipped options (skip=False, gLN, non-causal,
-relu or softmax mask), kernel size P = 3 / 5 / 7, channel counts that are multiples of 8 (N up to 512: the paper's N = 512, L = 16 encoder
+HIP kernels through the C ABI; a CPU tensor raises SehipError.  Built: skip=False, norm_type 'gLN' (shipped) or 'cLN', causal or
+not (causal=True moves the second PReLU / norm keys of every block one slot, as the reference's Chomp1d does), relu or softmax
+mask, kernel size P = 3 / 5 / 7, channel counts that are multiples of 8 (N up to 512: the paper's N = 512, L = 16 encoder
 included; B, H up to 512).
 """
 import math
@@ -83,8 +84,9 @@ class ConvTasNet(FlatModule):
         leave the 1x1 products' launches for sehip_ctn_gln_stats, every per-utterance sum of csrc/tasnet.hip goes through per-workgroup
         slots added in a fixed order by a second small launch (csrc/det.h), the column sums add their rows in row order, the weight
         gradients take the library's fixed-order kernels, the optimizer the unfused tail, and the whole step runs on ONE queue
-        (plan_tasnet.TasNetWorkspace.forward says why).  Two runs of the same steps are then bit-identical
-        (tests/test_gpu_deterministic.py)."""
+        (plan_tasnet.TasNetWorkspace.forward says why).  norm_type='cLN' has no per-utterance sums: its kernels' per-frame sums have one
+        order always, and the column sums of sehip_ctn_cln_bwd add their rows in row order.  Two runs of the same steps are then
+        bit-identical (tests/test_gpu_deterministic.py, tests/test_gpu_convtasnet_variants.py)."""
         self._deterministic = bool(on)
         return self
 

@@ -1,12 +1,14 @@
-"""Host-side plan of the ConvTasNet train step on libsehip (reference: src/model/conv_tasnet.py:34-487 with the shipped options
-skip=False, norm_type="gLN", non-causal, mask_nonlinear="relu"; BASELINE config C4).
+"""Host-side plan of the ConvTasNet train step on libsehip (reference: src/model/conv_tasnet.py:34-487 with skip=False;
+norm_type "gLN" (shipped) or "cLN", causal or not, mask_nonlinear "relu" or "softmax"; BASELINE config C4 is the shipped default).
 
 Activations are channels-last bf16 ``[M][K][C]`` (M utterances, K = (T - L)/(L/2) + 1 frames).  Every 1x1 convolution (bottleneck,
 the two pointwise convolutions of each of the R*X temporal blocks, the mask convolution) is a dense product of the implicit-GEMM
 engine (csrc/gemm.hip; the block's residual add rides in the product's epilogue through the descriptor's `res`), everything
 else -- encoder + cLN, PReLU + global LayerNorm, the depthwise dilated convolution, mask * mixture_w + basis + overlap-add -- the
 streaming kernels of csrc/tasnet.hip.  Per temporal block the forward pass is 2 products + 3 streams, the backward pass
-4 products + 4 streams.
+4 products + 4 streams.  norm_type="cLN" (csrc/tasnet_cln.hip): every sum of the normalisation is per frame, so there are no
+statistics records and no reduce pass -- 2 products + 2 streams forward, 4 products + 2 one-pass streams (+ their column sums) backward.
+causal=True moves the depthwise taps (centre P - 1 instead of P/2) and, as in the reference, the checkpoint keys behind Chomp1d.
 """
 import ctypes as C
 import os
@@ -25,9 +27,14 @@ class TasNetConfig:
 
     def __init__(self, sources, N=128, L=40, B=128, H=256, P=3, X=7, R=2, audio_channels=2, norm_type="gLN", causal=False,
                  mask_nonlinear="relu", sample_rate=44100, segment_length=44100 * 2 * 4, skip=False, **_ignored):
-        if skip or norm_type != "gLN" or causal or mask_nonlinear not in ("relu", "softmax"):
-            raise SehipError("sehip ConvTasNet: the shipped options (skip=False, norm_type='gLN', causal=False) with "
-                             "mask_nonlinear='relu' or 'softmax' are built")
+        if skip:
+            raise SehipError("sehip ConvTasNet: skip=True is not built (skip=False, norm_type 'gLN' or 'cLN', causal or not, "
+                             "mask_nonlinear 'relu' or 'softmax' are)")
+        if norm_type not in ("gLN", "cLN"):
+            raise SehipError(f"sehip ConvTasNet: norm_type={norm_type!r} is not built ('gLN' and 'cLN' are; 'BN' and 'id' are not)")
+        if mask_nonlinear not in ("relu", "softmax"):
+            raise SehipError("sehip ConvTasNet: mask_nonlinear must be 'relu' or 'softmax'")
+        self.norm_type, self.causal = norm_type, bool(causal)
         if mask_nonlinear == "softmax" and len(sources) > 8:
             raise SehipError("sehip ConvTasNet: mask_nonlinear='softmax' is built for at most 8 sources")
         self.mask_nonlinear = mask_nonlinear
@@ -50,7 +57,14 @@ class TasNetConfig:
         self.audio_channels = audio_channels
 
     def key(self):
-        return (self.C, self.N, self.L, self.B, self.H, self.P, self.X, self.R, self.audio_channels, self.mask_nonlinear)
+        return (self.C, self.N, self.L, self.B, self.H, self.P, self.X, self.R, self.audio_channels, self.mask_nonlinear,
+                self.norm_type, self.causal)
+
+    def inner_names(self, q):
+        """Names of the second PReLU and the second norm of the block with prefix q: Chomp1d takes slot 1 of the inner Sequential
+        when causal (src/model/conv_tasnet.py:374-383), so they sit one slot further."""
+        o = 1 if self.causal else 0
+        return q + f"3.net.{1 + o}.weight", q + f"3.net.{2 + o}.gamma", q + f"3.net.{2 + o}.beta"
 
     def blocks(self):
         return [(r, x) for r in range(self.R) for x in range(self.X)]
@@ -64,11 +78,12 @@ class TasNetConfig:
                ("separator.network.1.weight", (B, N, 1), "param")]
         for r, x in self.blocks():
             q = f"separator.network.2.{r}.{x}.net."
+            a2, g2, b2 = self.inner_names(q)
             out += [(q + "0.weight", (H, B, 1), "param"), (q + "1.weight", (1,), "param"),
                     (q + "2.gamma", (1, H, 1), "param"), (q + "2.beta", (1, H, 1), "param"),
                     (q + "3.pointwise_conv.weight", (B, H, 1), "param"),
-                    (q + "3.net.0.weight", (H, 1, P), "param"), (q + "3.net.1.weight", (1,), "param"),
-                    (q + "3.net.2.gamma", (1, H, 1), "param"), (q + "3.net.2.beta", (1, H, 1), "param")]
+                    (q + "3.net.0.weight", (H, 1, P), "param"), (a2, (1,), "param"),
+                    (g2, (1, H, 1), "param"), (b2, (1, H, 1), "param")]
         out += [("separator.network.3.weight", (self.C * N, B, 1), "param"),
                 ("decoder.basis_signals.weight", (self.audio_channels * L, N), "param")]
         return out
@@ -101,6 +116,7 @@ class TasNetStatic:
         dense("bott.fwd", net + "1.weight", N, B, "cln", "x0", "fwd")
         dense("bott.dg", net + "1.weight", B, N, "dx0", "dcln", "dgrad", transposed=True)
         self.blocks = cfg.blocks()
+        self.inner = [cfg.inner_names(f"{net}2.{r}.{x}.net.") for r, x in self.blocks]      # (second PReLU, gamma, beta) per block
         for b, (r, x) in enumerate(self.blocks):
             q = f"{net}2.{r}.{x}.net."
             dense(f"b{b}.in.fwd", q + "0.weight", B, H, f"x{b}", f"h1_{b}", "fwd")
@@ -159,8 +175,9 @@ class TasNetStatic:
             q = f"separator.network.2.{r}.{x}.net."
             o = self.blk_g_off[b]
             lin(q + "2.gamma", o["gch1"]); lin(q + "2.beta", o["gch1"] + H); lin(q + "3.net.0.weight", o["gch1"] + 2 * H)
-            lin(q + "3.net.2.gamma", o["gch2"]); lin(q + "3.net.2.beta", o["gch2"] + H)
-            lin(q + "1.weight", o["a1"]); lin(q + "3.net.1.weight", o["a2"])
+            a2, g2, b2 = cfg.inner_names(q)
+            lin(g2, o["gch2"]); lin(b2, o["gch2"] + H)
+            lin(q + "1.weight", o["a1"]); lin(a2, o["a2"])
         p = np.concatenate(ps).astype(np.int64)
         g = np.concatenate(gs).astype(np.int64)
         assert len(np.unique(p)) == len(p), "every ConvTasNet parameter has exactly one packed-gradient entry"
@@ -213,7 +230,8 @@ class TasNetWorkspace:
         self.stats = torch.zeros(nb, 2, M, 2, dtype=torch.float64, device=device)      # forward: (sum, sumsq) per block / gLN / utterance
         self.bsums = torch.zeros(nb, 2, M, 2, dtype=torch.float64, device=device)      # backward: (S1, S2)
         self.gpack = torch.zeros(st.n_gpack, dtype=torch.float32, device=device)
-        self.gln_scratch = torch.empty(int(_lib.lib().sehip_ctn_gln_bwd_scratch_floats(M, K, H)), dtype=torch.float32, device=device)
+        scratch_floats = _lib.lib().sehip_ctn_cln_bwd_scratch_floats if cfg.norm_type == "cLN" else _lib.lib().sehip_ctn_gln_bwd_scratch_floats
+        self.gln_scratch = torch.empty(int(scratch_floats(M, K, H)), dtype=torch.float32, device=device)
         self.codec_scratch = torch.empty(int(_lib.lib().sehip_ctn_codec_bwd_scratch_floats(M, K, N, cfg.L, cfg.audio_channels)),
                                          dtype=torch.float32, device=device)
         self.wav = None
@@ -274,7 +292,7 @@ class TasNetWorkspace:
         # round 6: the gLN statistics of every block's first 1x1 output inside the product's launch, where the dense-row kernel takes it
         # (sehip_gemm_desc.gln_stats; SEHIP_CTN_NO_FUSED_GLN=1: the separate sehip_ctn_gln_stats pass)
         lib_ = _lib.lib()
-        self.fused_gln = (not os.environ.get("SEHIP_CTN_NO_FUSED_GLN") and len(st.blocks) > 0 and
+        self.fused_gln = (st.cfg.norm_type == "gLN" and not os.environ.get("SEHIP_CTN_NO_FUSED_GLN") and len(st.blocks) > 0 and
                           all(int(lib_.sehip_gemm_takes_gln_stats(C.byref(self.desc[f"b{i}.in.fwd"]))) == 1 for i in range(len(st.blocks))))
 
     def gemm(self, name):
@@ -333,6 +351,14 @@ class TasNetWorkspace:
         self.gemm("bott.fwd")
         for i, (r, x) in enumerate(st.blocks):
             q = f"{net}2.{r}.{x}.net."
+            a2, g2, b2 = st.inner[i]
+            if cfg.norm_type == "cLN":      # per-frame moments inside the kernels: no statistics, nothing for the product's epilogue to do
+                self.gemm(f"b{i}.in.fwd")
+                call("sehip_ctn_cln_dwconv_fwd", b[f"h1_{i}"].ptr, pp(q + "1.weight"), pp(q + "2.gamma"), pp(q + "2.beta"),
+                     pp(q + "3.net.0.weight"), cfg.P, 2 ** x, int(cfg.causal), M, K, H, b[f"h2_{i}"].ptr, stream())
+                call("sehip_ctn_cln_apply", b[f"h2_{i}"].ptr, pp(a2), pp(g2), pp(b2), M, K, H, b[f"u{i}"].ptr, stream())
+                self.gemm(f"b{i}.pw.fwd")
+                continue
             s1 = self.stats[i, 0].data_ptr(); s2 = self.stats[i, 1].data_ptr()
             if fused_gln:           # the product's launch also takes the gLN statistics of what it stores (csrc/dgemm.hip)
                 d = self.desc[f"b{i}.in.fwd"]
@@ -341,10 +367,9 @@ class TasNetWorkspace:
             else:
                 self.gemm(f"b{i}.in.fwd")
                 call("sehip_ctn_gln_stats", b[f"h1_{i}"].ptr, pp(q + "1.weight"), M, K, H, s1, stream())
-            call("sehip_ctn_dwconv_fwd", b[f"h1_{i}"].ptr, pp(q + "1.weight"), s1, pp(q + "2.gamma"), pp(q + "2.beta"),
-                 pp(q + "3.net.0.weight"), cfg.P, 2 ** x, pp(q + "3.net.1.weight"), M, K, H, b[f"h2_{i}"].ptr, s2, stream())
-            call("sehip_ctn_gln_apply", b[f"h2_{i}"].ptr, pp(q + "3.net.1.weight"), s2, pp(q + "3.net.2.gamma"), pp(q + "3.net.2.beta"),
-                 M, K, H, b[f"u{i}"].ptr, stream())
+            call("sehip_ctn_dwconv_fwd_causal" if cfg.causal else "sehip_ctn_dwconv_fwd", b[f"h1_{i}"].ptr, pp(q + "1.weight"), s1,
+                 pp(q + "2.gamma"), pp(q + "2.beta"), pp(q + "3.net.0.weight"), cfg.P, 2 ** x, pp(a2), M, K, H, b[f"h2_{i}"].ptr, s2, stream())
+            call("sehip_ctn_gln_apply", b[f"h2_{i}"].ptr, pp(a2), s2, pp(g2), pp(b2), M, K, H, b[f"u{i}"].ptr, stream())
             self.gemm(f"b{i}.pw.fwd")
         self.gemm("mask.fwd")
         if not self._one_clear:
@@ -384,12 +409,20 @@ class TasNetWorkspace:
             self.wgrad(f"b{i}.pw.fwd")
             self.gemm(f"b{i}.pw.dg")
             du, dh2 = b[st.du_name(i)], b[st.dh2_name(i)]
-            call("sehip_ctn_gln_bwd", du.ptr, b[f"h2_{i}"].ptr, pp(q + "3.net.1.weight"), self.stats[i, 1].data_ptr(),
-                 pp(q + "3.net.2.gamma"), pp(q + "3.net.2.beta"), pp(q + "3.net.0.weight"), cfg.P, 2 ** x, 0, M, K, H,
-                 self.bsums[i, 1].data_ptr(), gp(o["gch2"]), dh2.ptr, gp(o["a2"]), ptr(self.gln_scratch), stream())
-            call("sehip_ctn_gln_bwd", dh2.ptr, b[f"h1_{i}"].ptr, pp(q + "1.weight"), self.stats[i, 0].data_ptr(),
-                 pp(q + "2.gamma"), pp(q + "2.beta"), pp(q + "3.net.0.weight"), cfg.P, 2 ** x, 1, M, K, H,
-                 self.bsums[i, 0].data_ptr(), gp(o["gch1"]), b[f"dh1_{i}"].ptr, gp(o["a1"]), ptr(self.gln_scratch), stream())
+            a2, g2, b2 = st.inner[i]
+            if cfg.norm_type == "cLN":      # one pass each: the sums of the normalisation's gradient are per frame
+                call("sehip_ctn_cln_bwd", du.ptr, b[f"h2_{i}"].ptr, pp(a2), pp(g2), pp(b2), pp(q + "3.net.0.weight"), cfg.P, 2 ** x, 0,
+                     int(cfg.causal), M, K, H, gp(o["gch2"]), dh2.ptr, gp(o["a2"]), ptr(self.gln_scratch), stream())
+                call("sehip_ctn_cln_bwd", dh2.ptr, b[f"h1_{i}"].ptr, pp(q + "1.weight"), pp(q + "2.gamma"), pp(q + "2.beta"),
+                     pp(q + "3.net.0.weight"), cfg.P, 2 ** x, 1, int(cfg.causal), M, K, H, gp(o["gch1"]), b[f"dh1_{i}"].ptr, gp(o["a1"]),
+                     ptr(self.gln_scratch), stream())
+            else:
+                call("sehip_ctn_gln_bwd", du.ptr, b[f"h2_{i}"].ptr, pp(a2), self.stats[i, 1].data_ptr(),
+                     pp(g2), pp(b2), pp(q + "3.net.0.weight"), cfg.P, 2 ** x, 0, M, K, H,
+                     self.bsums[i, 1].data_ptr(), gp(o["gch2"]), dh2.ptr, gp(o["a2"]), ptr(self.gln_scratch), stream())
+                call("sehip_ctn_gln_bwd_causal" if cfg.causal else "sehip_ctn_gln_bwd", dh2.ptr, b[f"h1_{i}"].ptr, pp(q + "1.weight"),
+                     self.stats[i, 0].data_ptr(), pp(q + "2.gamma"), pp(q + "2.beta"), pp(q + "3.net.0.weight"), cfg.P, 2 ** x, 1, M, K, H,
+                     self.bsums[i, 0].data_ptr(), gp(o["gch1"]), b[f"dh1_{i}"].ptr, gp(o["a1"]), ptr(self.gln_scratch), stream())
             self._chain_dirty = True
             self.wgrad(f"b{i}.in.fwd")
             self.gemm(f"b{i}.in.dg")
