@@ -662,6 +662,52 @@ long sehip_dmx_attn_bwd_scratch_floats(int B, int T, int hid);
 int sehip_dmx_attn_bwd(const void* qkv, const void* dres, int B, int T, int hid, int heads, int nd, int NQ, float* slabs, void* dqkv_bf16,
                        void* stream);
 
+/* ---- Wave-U-Net (src/model/wav_unet.py:8-110): everything around the convolutions' products (csrc/wavunet.hip).  Activations are
+ *      channels-last bf16 [B][T_l][C] (T_l = T / 2^l, C a multiple of 8 up to 2048); the waveform x [B][T] and the output stay fp32.
+ *      Every sum goes through one row of partials per workgroup (scratch: the *_scratch_floats() sizes, caller-owned, no need to
+ *      clear) added in a fixed order: no atomics, two runs are bit-identical.
+ *      enc0_fwd      : y0 [B][T][C0] bf16 = Conv1d(1 -> C0, k = 15, pad 7)(x) + bias (:12, W [C0][1][15]); x is not rounded
+ *      enc0_wgrad    : dW [C0][15], db [C0] from dy0 and x (no input gradient: the waveform needs none)
+ *      bn_stats      : per-channel sums of y [rows][C] about the channel's value in row 0 (a mean far above the deviation costs no
+ *                      variance); bn_finalize: coef [C][4] = (scale, shift, mean, rstd) of nn.BatchNorm1d (:14) from them
+ *                      (training: biased variance for the normalisation, running_mean / running_var (unbiased) / num_batches_tracked
+ *                      updated) or from the running statistics (training == 0: part and y may be NULL)
+ *      bn_apply      : z = LeakyReLU_0.1(scale y + shift) (:15) -- the encoder's skip tensor; the [::2] that follows (:89) is the next
+ *                      product's view of z, not a kernel
+ *      bn_apply_up2  : up [B][2 Tin][C] = F.interpolate(z, scale_factor=2, mode="linear", align_corners=True) (:100) of the same z,
+ *                      which is never stored; source frame and weight in integers: p (Tin - 1) = i (2 Tin - 1) + r, weight r / (2 Tin - 1)
+ *      up2_bwd       : dz [B][Tin][C] from dup [B][2 Tin][C]: frame i gathers output positions 2 i - 2 .. 2 i + 2
+ *      bn_bwd_reduce / _finalize / _apply : backward of affine + LeakyReLU + batch statistics.  The incoming gradient of row r is
+ *                      dz_full[r] + (r even ? dz_even[r / 2] : 0), dz_even [rows / 2][C] optional (an encoder layer: the decoder's skip
+ *                      half of the concat gradient + the next convolution's input gradient on the decimated frames).  PRECONDITION with
+ *                      dz_even: rows = B T with T EVEN for every utterance, so that a row's parity is its frame's; the entry points
+ *                      can only check rows % 2 == 0 -- an odd T with an even B would pair frames across utterances.  z is recomputed
+ *                      from y and coef.  finalize writes dgamma [C], dbeta [C] and bcoef [C][4]
+ *      out_fwd       : out [rows] fp32 = tanh(sum_c W[c] z[r][c] + W[C0] x[r] + b): Conv1d(1 + C0 -> 1, k = 1) on cat([o, input]) + Tanh
+ *                      (:74-77, :107-109)
+ *      out_bwd       : dz [rows][C0] bf16 = dout (1 - out^2) W[c]; dW [C0 + 1], db [1] */
+long sehip_wun_bn_scratch_floats(long rows, int C);
+long sehip_wun_enc0_wgrad_scratch_floats(int B, int T, int C0);
+long sehip_wun_out_bwd_scratch_floats(long rows, int C0);
+int sehip_wun_enc0_fwd(const float* x, const float* W, const float* bias, int B, int T, int C0, void* y0, void* stream);
+int sehip_wun_enc0_wgrad(const void* dy0, const float* x, int B, int T, int C0, float* dW, float* db, float* scratch, void* stream);
+int sehip_wun_bn_stats(const void* y, long rows, int C, float* part, void* stream);
+int sehip_wun_bn_finalize(const float* part, const void* y, const float* gamma, const float* beta, float* running_mean,
+                          float* running_var, long* num_batches_tracked, long rows, int C, float eps, float momentum, int training,
+                          float* coef, void* stream);
+int sehip_wun_bn_apply(const void* y, const float* coef, long rows, int C, void* z, void* stream);
+int sehip_wun_bn_apply_up2(const void* y, const float* coef, int B, int Tin, int C, void* up, void* stream);
+int sehip_wun_up2_bwd(const void* dup, int B, int Tin, int C, void* dz, void* stream);
+int sehip_wun_bn_bwd_reduce(const void* dz_full, const void* dz_even, const void* y, const float* coef, long rows, int C, float* part,
+                            void* stream);
+int sehip_wun_bn_bwd_finalize(const float* part, const float* coef, long rows, int C, float* dgamma, float* dbeta, float* bcoef,
+                              void* stream);
+int sehip_wun_bn_bwd_apply(const void* dz_full, const void* dz_even, const void* y, const float* coef, const float* bcoef, long rows,
+                           int C, void* dy, void* stream);
+int sehip_wun_out_fwd(const void* z, const float* x, const float* W, const float* bias, long rows, int C0, float* out, void* stream);
+int sehip_wun_out_bwd(const float* dout, const float* out, const void* z, const float* x, const float* W, long rows, int C0, void* dz,
+                      float* dW, float* db, float* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

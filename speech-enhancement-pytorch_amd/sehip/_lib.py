@@ -170,8 +170,24 @@ _PROTOS = {
     "sehip_lstm2_bwd": [P, P, P, P, P, P, P, P, P, I, I, I, P, P, P, P, P, P, U, P],
     "sehip_lstm_fwd_chunk": [P, P, P, I, I, I, I, I, P, P, P, P],
     "sehip_lstm_bwd_chunk": [P, P, P, P, P, I, I, I, I, I, P, P, P, P],
+    "sehip_wun_bn_scratch_floats": [L, I],
+    "sehip_wun_enc0_wgrad_scratch_floats": [I, I, I],
+    "sehip_wun_out_bwd_scratch_floats": [L, I],
+    "sehip_wun_enc0_fwd": [P, P, P, I, I, I, P, P],
+    "sehip_wun_enc0_wgrad": [P, P, I, I, I, P, P, P, P],
+    "sehip_wun_bn_stats": [P, L, I, P, P],
+    "sehip_wun_bn_finalize": [P, P, P, P, P, P, P, L, I, F, F, I, P, P],
+    "sehip_wun_bn_apply": [P, P, L, I, P, P],
+    "sehip_wun_bn_apply_up2": [P, P, I, I, I, P, P],
+    "sehip_wun_up2_bwd": [P, I, I, I, P, P],
+    "sehip_wun_bn_bwd_reduce": [P, P, P, P, L, I, P, P],
+    "sehip_wun_bn_bwd_finalize": [P, P, L, I, P, P, P, P],
+    "sehip_wun_bn_bwd_apply": [P, P, P, P, P, L, I, P, P],
+    "sehip_wun_out_fwd": [P, P, P, P, L, I, P, P],
+    "sehip_wun_out_bwd": [P, P, P, P, P, L, I, P, P, P, P, P],
 }
-_RESTYPE = {"sehip_lstm2_gran_bytes": C.c_long, "sehip_dmx_attn_bwd_scratch_floats": C.c_long, "sehip_ctn_codec_bwd_scratch_floats": C.c_long, "sehip_ctn_gln_bwd_scratch_floats": C.c_long, "sehip_ctn_cln_bwd_scratch_floats": C.c_long, "sehip_wgrad_group_bytes": C.c_long, "sehip_wgrad_dense_group_bytes": C.c_long, "sehip_cbn_scratch_floats": C.c_long, "sehip_rbn_scratch_floats": C.c_long, "sehip_dcunet_tail_scratch_floats": C.c_long, "sehip_event_create": C.c_void_p, "sehip_stream_create": C.c_void_p}
+_RESTYPE = {"sehip_wun_bn_scratch_floats": C.c_long, "sehip_wun_enc0_wgrad_scratch_floats": C.c_long, "sehip_wun_out_bwd_scratch_floats": C.c_long,
+            "sehip_lstm2_gran_bytes": C.c_long, "sehip_dmx_attn_bwd_scratch_floats": C.c_long, "sehip_ctn_codec_bwd_scratch_floats": C.c_long, "sehip_ctn_gln_bwd_scratch_floats": C.c_long, "sehip_ctn_cln_bwd_scratch_floats": C.c_long, "sehip_wgrad_group_bytes": C.c_long, "sehip_wgrad_dense_group_bytes": C.c_long, "sehip_cbn_scratch_floats": C.c_long, "sehip_rbn_scratch_floats": C.c_long, "sehip_dcunet_tail_scratch_floats": C.c_long, "sehip_event_create": C.c_void_p, "sehip_stream_create": C.c_void_p}
 
 
 def lib():

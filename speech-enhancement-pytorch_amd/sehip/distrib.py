@@ -15,10 +15,12 @@ from .model.conv_tasnet import ConvTasNet
 from .model.dcunet import DCUnet
 from .model.dnn import DeepNeuralNetwork
 from .model.demucs import Demucs
+from .model.wav_unet import WavUnet
 from .optim import FlatOptimizer
 from .utils import obj2dict
 
-MODEL_REGISTRY = {"dccrn": DCCRN, "dcunet": DCUnet, "dnn": DeepNeuralNetwork, "conv-tasnet": ConvTasNet, "demucs": Demucs}
+MODEL_REGISTRY = {"dccrn": DCCRN, "dcunet": DCUnet, "dnn": DeepNeuralNetwork, "conv-tasnet": ConvTasNet, "demucs": Demucs,
+                  "wav-unet": WavUnet}
 _REFERENCE_NAMES = ("dnn", "mel-rnn", "unet", "dccrn", "dcunet", "demucs", "wav-unet", "conv-tasnet", "crn", "rnn-stft-mask")
 
 
