@@ -6,13 +6,25 @@
 //   loss  = -mean_rows(l_row)
 //
 // HBM-bound: one 256-thread workgroup per utterance row; the row is read twice (dot products, then the
-// exact residual energy -- the second read hits L2), the backward is one fused a*x+b*s pass whose two row
-// coefficients were produced by the forward.
+// exact residual energy -- the second read hits L2), the backward is one fused a*(x - alpha*s) + b*s pass whose three
+// row coefficients were produced by the forward.
 #include "common.h"
 
 #define EPS 1e-8f
 
-// rowstat[r] = {a, b, l_row, unused}; d loss / d x_j = upstream * (a*x_j + b*s_j)
+// e = x - alpha*s, rounded as a product and a difference in EVERY kernel that forms it.  The backward's a*e cancels against the
+// 2 q <e, s> / (<s, s> + eps) * s part of b*s whenever e is all but parallel to s (a one-sample row is the extreme), and it does so
+// only if its e is bit for bit the e whose <e, s> the forward summed: no contraction to an fma here, in one kernel and not in another.
+__device__ __forceinline__ float sisnr_residual(float x, float alpha, float s) {
+    float t = alpha * s;
+    asm volatile("" : "+v"(t));   // (-ffp-contract=fast overrides a contract(off) pragma; the product is pinned in a register instead)
+    return x - t;
+}
+
+// rowstat[r] = {a, b, l_row, alpha}; d loss / d x_j = upstream * (a*(x_j - alpha*s_j) + b*s_j): the residual e = x - alpha s is formed
+// per element, as the forward and the reference's autograd form it.  Folding alpha into the coefficient of s (a*x + (b - a*alpha)*s)
+// is the same polynomial, but its two terms are each |a| |x| large and cancel down to |a| |e|: at 40 / 60 dB the rounding of the
+// folded form is 3 x the reference's own fp32 deviation from float64, and a one-sample row loses its gradient altogether.
 // (1024 threads: a row is two dependent passes of one workgroup, 32 rows per step -- latency, not bandwidth: 23.6 us with 256 threads)
 __global__ __launch_bounds__(1024) void sisnr_fwd_kernel(const float* __restrict__ est, const float* __restrict__ ref,
                                                         int n, int rows, float4* __restrict__ rowstat) {
@@ -42,14 +54,15 @@ __global__ __launch_bounds__(1024) void sisnr_fwd_kernel(const float* __restrict
         for (int i = threadIdx.x; i < n4; i += 1024) {
             float4 a = x4[i], b = s4[i];
             float t0 = alpha * b.x, t1 = alpha * b.y, t2 = alpha * b.z, t3 = alpha * b.w;
-            float e0 = a.x - t0, e1 = a.y - t1, e2 = a.z - t2, e3 = a.w - t3;
+            float e0 = sisnr_residual(a.x, alpha, b.x), e1 = sisnr_residual(a.y, alpha, b.y), e2 = sisnr_residual(a.z, alpha, b.z),
+                  e3 = sisnr_residual(a.w, alpha, b.w);
             et += t0 * t0 + t1 * t1 + t2 * t2 + t3 * t3;
             en += e0 * e0 + e1 * e1 + e2 * e2 + e3 * e3;
             es += e0 * b.x + e1 * b.y + e2 * b.z + e3 * b.w;
         }
     } else {
         for (int i = threadIdx.x; i < n; i += 1024) {
-            float t = alpha * s[i], e = x[i] - t;
+            float t = alpha * s[i], e = sisnr_residual(x[i], alpha, s[i]);
             et += t * t; en += e * e; es += e * s[i];
         }
     }
@@ -63,7 +76,7 @@ __global__ __launch_bounds__(1024) void sisnr_fwd_kernel(const float* __restrict
         const float c = -(1.0f / rows) * 10.f / (2.302585092994046f * (ratio + EPS));
         const float q = et / ((en + EPS) * (en + EPS));
         const float a = c * (-2.f * q);
-        const float b = c * (2.f * alpha * ss / ((ss + EPS) * (en + EPS)) + 2.f * q * alpha + 2.f * q * es / (ss + EPS));
+        const float b = c * (2.f * alpha * ss / ((ss + EPS) * (en + EPS)) + 2.f * q * es / (ss + EPS));
         rowstat[r] = make_float4(a, b, l, alpha);
     }
 }
@@ -82,10 +95,12 @@ __global__ __launch_bounds__(256) void sisnr_bwd_kernel(const float* __restrict_
     const int r = blockIdx.y;
     const float4 st = rowstat[r];
     const float up = upstream ? upstream[0] : 1.f;
-    const float a = st.x * up, b = st.y * up;
+    const float a = st.x * up, b = st.y * up, alpha = st.w;
     const size_t base = (size_t)r * n;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256)
-        dest[base + i] = a * est[base + i] + b * ref[base + i];
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        const float s = ref[base + i];
+        dest[base + i] = a * sisnr_residual(est[base + i], alpha, s) + b * s;
+    }
 }
 
 // SI-SDR validation metric (src/metric.py:92-123, SI_SDR): per row alpha = <e,r> / (<r,r> + eps), ratio = |alpha r|^2 /
@@ -176,7 +191,7 @@ __global__ __launch_bounds__(256) void sisnr_pit_rows_kernel(const float* __rest
     const float alpha = xs / (ss + EPS);
     float et = 0.f, en = 0.f, es = 0.f;
     for (int k = threadIdx.x; k < n; k += 256) {
-        const float t = alpha * s[k], e = x[k] - t;
+        const float t = alpha * s[k], e = sisnr_residual(x[k], alpha, s[k]);
         et += t * t; en += e * e; es += e * s[k];
     }
     et = block_sum<4>(et, red);
@@ -189,7 +204,7 @@ __global__ __launch_bounds__(256) void sisnr_pit_rows_kernel(const float* __rest
         const float cc = -(1.0f / ((float)S * (float)R)) * 10.f / (2.302585092994046f * (ratio + EPS));
         const float q = et / ((en + EPS) * (en + EPS));
         const float a = cc * (-2.f * q);
-        const float bb = cc * (2.f * alpha * ss / ((ss + EPS) * (en + EPS)) + 2.f * q * alpha + 2.f * q * es / (ss + EPS));
+        const float bb = cc * (2.f * alpha * ss / ((ss + EPS) * (en + EPS)) + 2.f * q * es / (ss + EPS));
         rowstat[(size_t)pair * R + r] = make_float4(a, bb, l, alpha);
     }
 }
@@ -241,9 +256,12 @@ __global__ __launch_bounds__(256) void sisnr_pit_bwd_kernel(const float* __restr
     const int b = r / C, c = r - b * C;
     const float4 st = rowstat[(size_t)(i * S + j) * R + r];
     const float up = upstream ? upstream[0] : 1.f;
-    const float a = st.x * up, bb = st.y * up;
+    const float a = st.x * up, bb = st.y * up, alpha = st.w;
     const size_t xb = (((size_t)b * S + i) * C + c) * n, sb = (((size_t)b * S + j) * C + c) * n;
-    for (int k = blockIdx.x * 256 + threadIdx.x; k < n; k += gridDim.x * 256) dest[xb + k] = a * est[xb + k] + bb * ref[sb + k];
+    for (int k = blockIdx.x * 256 + threadIdx.x; k < n; k += gridDim.x * 256) {
+        const float s = ref[sb + k];
+        dest[xb + k] = a * sisnr_residual(est[xb + k], alpha, s) + bb * s;       // the residual form of sisnr_bwd_kernel
+    }
 }
 
 extern "C" int sehip_sisnr_pit_fwd(const float* est, const float* ref, int B, int S, int C, int n, float* rowstat, float* pairloss,
