@@ -98,6 +98,19 @@ int sehip_sisnr_pit_fwd(const float* est, const float* ref, int B, int S, int C,
 int sehip_sisnr_pit_bwd(const float* est, const float* ref, const float* rowstat, const int* perm, const float* upstream /*or NULL*/,
                         int B, int S, int C, int n, float* dest, void* stream);
 
+/* ---- permutation-invariant l1 / mse: the same loss around torch.nn.functional.l1_loss / mse_loss (mode 0 / 1; the reference's
+ *      shipped `optim.loss: 'mse'`).  est / ref [B][S][C][n] fp32, S <= 6; pair (i, j) = mean over everything but the speaker.
+ *      One pass over the data fills partials[sehip_pit_pointwise_blocks(B, S, C, n)][S*S] (workspace, no atomics: the same bits
+ *      with and without sehip_set_deterministic); a single wave then writes pairloss [S*S], perm [S] int32 (perm[j] = estimated
+ *      speaker matched with target j) and loss [1] = mean over the matched pairs.  bwd: dest = upstream / (S B C n) *
+ *      (sign(e_i - t_j) | 2 (e_i - t_j)), j read from perm on the device.  Nothing here synchronises: capturable into a hipGraph.
+ *      sehip_pit_pointwise_blocks is a host-only helper (0 for an invalid shape). */
+int sehip_pit_pointwise_blocks(int B, int S, int C, int n);
+int sehip_pit_pointwise_fwd(const float* est, const float* ref, int B, int S, int C, int n, int mode, float* partials,
+                            float* pairloss, int* perm, float* loss, void* stream);
+int sehip_pit_pointwise_bwd(const float* est, const float* ref, const int* perm, const float* upstream /*or NULL*/,
+                            int B, int S, int C, int n, int mode, float* dest, void* stream);
+
 /* ---- phase-sensitive spectral approximation loss: src/loss.py:32-56 (`optim.loss: psa`; the Solver passes the mixture's spectrum as
  *      the third argument, src/solver.py:480).  enh / tgt / mix: ncomplex (real, imaginary) pairs each;
  *      loss = mean_i (|E_i| - |T_i| cos(tanh(Ti / (Tr + 1e-9)) - tanh(Mi / (Mr + 1e-9))))^2   (the reference's formula as it stands).

@@ -209,18 +209,11 @@ __global__ __launch_bounds__(256) void sisnr_pit_rows_kernel(const float* __rest
     }
 }
 
-__global__ void sisnr_pit_select_kernel(const float4* __restrict__ rowstat, int R, int S, float* __restrict__ pairloss,
-                                        int* __restrict__ perm, float* __restrict__ loss) {
-    __shared__ float m[PIT_MAXS * PIT_MAXS];
-    for (int pair = 0; pair < S * S; ++pair) {            // single wave, fixed summation order
-        float acc = 0.f;
-        for (int r = threadIdx.x; r < R; r += 64) acc += rowstat[(size_t)pair * R + r].z;
-        acc = wave_sum(acc);
-        if (threadIdx.x == 0) { m[pair] = -acc / R; pairloss[pair] = -acc / R; }
-    }
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    int cur[PIT_MAXS], best[PIT_MAXS];
+// The reference's walk over the permutations (src/loss.py:73-86): itertools.permutations(range(S)) order, strict '<' from
+// lmin = 1e9, the sum over j of m[perm[j]][j] taken in fp32 in the order j = 0 .. S-1.  m is the S x S pair matrix (row =
+// estimated speaker); best[j] = estimated speaker matched with target j.  One thread.
+__device__ void pit_best_permutation(const float* m, int S, int* best) {
+    int cur[PIT_MAXS];
     for (int k = 0; k < S; ++k) cur[k] = best[k] = k;
     float lmin = 1e9f;
     for (;;) {
@@ -239,6 +232,21 @@ __global__ void sisnr_pit_select_kernel(const float4* __restrict__ rowstat, int 
         int t = cur[k]; cur[k] = cur[l2]; cur[l2] = t;
         for (int a = k + 1, b = S - 1; a < b; ++a, --b) { t = cur[a]; cur[a] = cur[b]; cur[b] = t; }
     }
+}
+
+__global__ void sisnr_pit_select_kernel(const float4* __restrict__ rowstat, int R, int S, float* __restrict__ pairloss,
+                                        int* __restrict__ perm, float* __restrict__ loss) {
+    __shared__ float m[PIT_MAXS * PIT_MAXS];
+    for (int pair = 0; pair < S * S; ++pair) {            // single wave, fixed summation order
+        float acc = 0.f;
+        for (int r = threadIdx.x; r < R; r += 64) acc += rowstat[(size_t)pair * R + r].z;
+        acc = wave_sum(acc);
+        if (threadIdx.x == 0) { m[pair] = -acc / R; pairloss[pair] = -acc / R; }
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    int best[PIT_MAXS];
+    pit_best_permutation(m, S, best);
     float tot = 0.f;
     for (int j = 0; j < S; ++j) { perm[j] = best[j]; tot += m[best[j] * S + j]; }
     loss[0] = tot / S;
@@ -400,5 +408,220 @@ extern "C" int sehip_pointwise_loss_bwd(const float* x, const float* y, long n, 
     if (grid > 2048) grid = 2048;
     pointwise_loss_bwd_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(x, y, n, mode, upstream, dx);
     SEHIP_CHECK_LAUNCH("pointwise_loss_bwd");
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Permutation-invariant l1 / mse: src/loss.py:58-100 around torch.nn.functional.l1_loss / mse_loss (the reference's shipped
+// `optim.loss: 'mse'`, `optim.pit: True`).  est / ref [B][S][C][n], speakers on axis 1; pair (i, j) is the mean over
+// everything but the speaker of |e_i - t_j| or (e_i - t_j)^2.
+//   pairs kernel : ONE pass over est and ref.  A workgroup owns `chunk` samples of one (b, c) row set, loads the S estimated and
+//                  S target values of every sample once and keeps all S*S sums in registers (S, the mode and the load width are
+//                  template parameters: 36 accumulators + 12 float4 at S = 6, no scratch); one record [S*S] per workgroup
+//                  goes to partials[nblocks][S*S].  No atomics: the sums do not depend on arrival order, so nothing switches on
+//                  sehip_deterministic().
+//   select kernel: one wave adds the records in a fixed order in double, divides by B*C*n, walks the permutations
+//                  (pit_best_permutation) and writes pairloss [S*S], perm [S], loss [1].
+//   bwd kernel   : dest[b,i,c,k] = upstream / (S B C n) * g(e_i - t_j), j read from perm on the device; g as in
+//                  pointwise_loss_bwd_kernel (sign with 0 at 0, or 2 d).
+// Rows start at ((b*S + i)*C + c)*n floats: the float4 variants need n % 4 == 0 and 16-byte aligned bases (then every row and
+// every chunk start is aligned: chunk is a multiple of 4), anything else takes the scalar variants (every n >= 1).
+// ------------------------------------------------------------------------------------------------
+#define PITPW_THREADS 256
+#define PITPW_CHUNK 2048L           // samples of one row per workgroup (two float4 per thread), doubled while the grid exceeds ...
+#define PITPW_MAXBLOCKS 1024L       // ... this many workgroups (the select kernel's single wave reads every record)
+#define PITPW_MAXROWS (1L << 20)    // B*C: the grid's x extent
+#define PITPW_MAXN (0x7fffffff - 64 * 4 * PITPW_THREADS)   // the loops' int sample index never wraps
+
+static long pitpw_chunk(long rows, long n) {
+    long chunk = PITPW_CHUNK;
+    while (rows * ((n + chunk - 1) / chunk) > PITPW_MAXBLOCKS && chunk < n) chunk *= 2;
+    return chunk;
+}
+
+extern "C" int sehip_pit_pointwise_blocks(int B, int S, int C, int n) {
+    if (B <= 0 || C <= 0 || n <= 0 || S < 1 || S > PIT_MAXS || (long)B * C > PITPW_MAXROWS || n > PITPW_MAXN) return 0;
+    const long rows = (long)B * C, chunk = pitpw_chunk(rows, n);
+    return (int)(rows * ((n + chunk - 1) / chunk));
+}
+
+template <int MODE>
+__device__ __forceinline__ float pitpw_term(float e, float t) {
+    const float d = e - t;
+    return MODE == 0 ? fabsf(d) : d * d;
+}
+
+template <int S, int MODE, bool VEC>
+__global__ __launch_bounds__(PITPW_THREADS) void pit_pointwise_pairs_kernel(const float* __restrict__ est, const float* __restrict__ ref,
+                                                                            int C, int n, int chunk, float* __restrict__ partials) {
+    __shared__ float red[PITPW_THREADS / 64][S * S];
+    const int r = blockIdx.x, b = r / C, c = r - b * C;    // grid (x: b*C + c, y: chunk of the row)
+    const size_t row0 = ((size_t)b * S * C + c) * n, sstride = (size_t)C * n;      // speaker i of this (b, c): row0 + i * sstride
+    const int k0 = blockIdx.y * chunk;                                             // < n: gridDim.y = ceil(n / chunk)
+    const int k1 = n - k0 < chunk ? n : k0 + chunk;
+    float acc[S * S];
+#pragma unroll
+    for (int p = 0; p < S * S; ++p) acc[p] = 0.f;
+    if (VEC) {
+        for (int k = k0 + 4 * (int)threadIdx.x; k < k1; k += 4 * PITPW_THREADS) {
+            float4 e[S], t[S];
+#pragma unroll
+            for (int i = 0; i < S; ++i) {
+                e[i] = *reinterpret_cast<const float4*>(est + row0 + i * sstride + k);
+                t[i] = *reinterpret_cast<const float4*>(ref + row0 + i * sstride + k);
+            }
+#pragma unroll
+            for (int i = 0; i < S; ++i)
+#pragma unroll
+                for (int j = 0; j < S; ++j)
+                    acc[i * S + j] += (pitpw_term<MODE>(e[i].x, t[j].x) + pitpw_term<MODE>(e[i].y, t[j].y)) +
+                                      (pitpw_term<MODE>(e[i].z, t[j].z) + pitpw_term<MODE>(e[i].w, t[j].w));
+        }
+    } else {
+        for (int k = k0 + (int)threadIdx.x; k < k1; k += PITPW_THREADS) {
+            float e[S], t[S];
+#pragma unroll
+            for (int i = 0; i < S; ++i) {
+                e[i] = est[row0 + i * sstride + k];
+                t[i] = ref[row0 + i * sstride + k];
+            }
+#pragma unroll
+            for (int i = 0; i < S; ++i)
+#pragma unroll
+                for (int j = 0; j < S; ++j) acc[i * S + j] += pitpw_term<MODE>(e[i], t[j]);
+        }
+    }
+    const int w = threadIdx.x >> 6;
+#pragma unroll
+    for (int p = 0; p < S * S; ++p) {
+        const float v = wave_sum(acc[p]);
+        if ((threadIdx.x & 63) == 0) red[w][p] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < S * S) {
+        float v = 0.f;
+#pragma unroll
+        for (int q = 0; q < PITPW_THREADS / 64; ++q) v += red[q][threadIdx.x];
+        partials[((size_t)blockIdx.x * gridDim.y + blockIdx.y) * (S * S) + threadIdx.x] = v;
+    }
+}
+
+template <int S>
+__global__ __launch_bounds__(64) void pit_pointwise_select_kernel(const float* __restrict__ partials, int nblocks, double inv_count,
+                                                                  float* __restrict__ pairloss, int* __restrict__ perm,
+                                                                  float* __restrict__ loss) {
+    __shared__ float m[S * S];
+    double acc[S * S];                                     // single wave: lane l adds records l, l + 64, ... in that order, then the
+#pragma unroll                                             // xor tree of wave_sum_d -- one fixed order whatever the schedule
+    for (int p = 0; p < S * S; ++p) acc[p] = 0.0;
+    for (int q = threadIdx.x; q < nblocks; q += 64) {
+        const float* rec = partials + (size_t)q * (S * S);
+#pragma unroll
+        for (int p = 0; p < S * S; ++p) acc[p] += (double)rec[p];
+    }
+#pragma unroll
+    for (int p = 0; p < S * S; ++p) {
+        const double v = wave_sum_d(acc[p]);
+        if (threadIdx.x == 0) { m[p] = (float)(v * inv_count); pairloss[p] = m[p]; }
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    int best[PIT_MAXS];
+    pit_best_permutation(m, S, best);
+    float tot = 0.f;
+    for (int j = 0; j < S; ++j) { perm[j] = best[j]; tot += m[best[j] * S + j]; }
+    loss[0] = tot / S;
+}
+
+template <int MODE>
+__device__ __forceinline__ float pitpw_grad(float e, float t, float up) {
+    const float d = e - t;
+    return MODE == 0 ? (d > 0.f ? up : (d < 0.f ? -up : 0.f)) : 2.f * d * up;
+}
+
+// grid (x: b*C + c, y: strides over the row, z: estimated speaker i)
+template <int MODE, bool VEC>
+__global__ __launch_bounds__(PITPW_THREADS) void pit_pointwise_bwd_kernel(const float* __restrict__ est, const float* __restrict__ ref,
+                                                                          const int* __restrict__ perm, const float* __restrict__ upstream,
+                                                                          int S, int C, int n, float scale, float* __restrict__ dest) {
+    const int r = blockIdx.x, i = blockIdx.z, b = r / C, c = r - b * C;
+    int j = 0;
+    for (int k = 0; k < S; ++k)
+        if (perm[k] == i) j = k;                           // the target this estimated speaker was matched with
+    const float up = (upstream ? upstream[0] : 1.f) * scale;
+    const size_t xb = (((size_t)b * S + i) * C + c) * n, sb = (((size_t)b * S + j) * C + c) * n;
+    if (VEC) {
+        const int n4 = n >> 2;
+        const float4* x4 = reinterpret_cast<const float4*>(est + xb);
+        const float4* s4 = reinterpret_cast<const float4*>(ref + sb);
+        float4* d4 = reinterpret_cast<float4*>(dest + xb);
+        for (int k = blockIdx.y * PITPW_THREADS + threadIdx.x; k < n4; k += gridDim.y * PITPW_THREADS) {
+            const float4 e = x4[k], t = s4[k];
+            d4[k] = make_float4(pitpw_grad<MODE>(e.x, t.x, up), pitpw_grad<MODE>(e.y, t.y, up), pitpw_grad<MODE>(e.z, t.z, up),
+                                pitpw_grad<MODE>(e.w, t.w, up));
+        }
+    } else {
+        for (int k = blockIdx.y * PITPW_THREADS + threadIdx.x; k < n; k += gridDim.y * PITPW_THREADS)
+            dest[xb + k] = pitpw_grad<MODE>(est[xb + k], ref[sb + k], up);
+    }
+}
+
+static bool pitpw_vec(const void* a, const void* b, const void* c, int n) {
+    return (n & 3) == 0 && ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0);
+}
+
+template <int S>
+static void pitpw_launch_fwd(const float* est, const float* ref, int B, int C, int n, int mode, float* partials, float* pairloss,
+                             int* perm, float* loss, hipStream_t st) {
+    const long rows = (long)B * C, chunk = pitpw_chunk(rows, n);
+    const dim3 grid((unsigned)rows, (unsigned)((n + chunk - 1) / chunk));
+    const bool vec = pitpw_vec(est, ref, nullptr, n);
+#define PITPW_PAIRS(MODE_, VEC_) \
+    pit_pointwise_pairs_kernel<S, MODE_, VEC_><<<grid, PITPW_THREADS, 0, st>>>(est, ref, C, n, (int)chunk, partials)
+    if (mode == 0) { if (vec) PITPW_PAIRS(0, true); else PITPW_PAIRS(0, false); }
+    else           { if (vec) PITPW_PAIRS(1, true); else PITPW_PAIRS(1, false); }
+#undef PITPW_PAIRS
+    pit_pointwise_select_kernel<S><<<1, 64, 0, st>>>(partials, (int)(grid.x * grid.y), 1.0 / ((double)B * C * n), pairloss, perm, loss);
+}
+
+extern "C" int sehip_pit_pointwise_fwd(const float* est, const float* ref, int B, int S, int C, int n, int mode, float* partials,
+                                       float* pairloss, int* perm, float* loss, void* stream) {
+    SEHIP_REQUIRE(S >= 1 && S <= PIT_MAXS, "pit_pointwise_fwd: S=%d outside [1, %d]", S, PIT_MAXS);
+    SEHIP_REQUIRE(mode == 0 || mode == 1, "pit_pointwise_fwd: mode=%d (0 = l1, 1 = mse)", mode);
+    SEHIP_REQUIRE(B > 0 && C > 0 && n > 0, "pit_pointwise_fwd: empty input (B=%d C=%d n=%d)", B, C, n);
+    SEHIP_REQUIRE((long)B * C <= PITPW_MAXROWS && n <= PITPW_MAXN, "pit_pointwise_fwd: shape too large (B*C=%ld n=%d)", (long)B * C, n);
+    SEHIP_REQUIRE(est && ref && partials && pairloss && perm && loss, "pit_pointwise_fwd: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    switch (S) {
+        case 1: pitpw_launch_fwd<1>(est, ref, B, C, n, mode, partials, pairloss, perm, loss, st); break;
+        case 2: pitpw_launch_fwd<2>(est, ref, B, C, n, mode, partials, pairloss, perm, loss, st); break;
+        case 3: pitpw_launch_fwd<3>(est, ref, B, C, n, mode, partials, pairloss, perm, loss, st); break;
+        case 4: pitpw_launch_fwd<4>(est, ref, B, C, n, mode, partials, pairloss, perm, loss, st); break;
+        case 5: pitpw_launch_fwd<5>(est, ref, B, C, n, mode, partials, pairloss, perm, loss, st); break;
+        default: pitpw_launch_fwd<6>(est, ref, B, C, n, mode, partials, pairloss, perm, loss, st); break;
+    }
+    SEHIP_CHECK_LAUNCH("pit_pointwise_fwd");
+    return 0;
+}
+
+extern "C" int sehip_pit_pointwise_bwd(const float* est, const float* ref, const int* perm, const float* upstream, int B, int S, int C,
+                                       int n, int mode, float* dest, void* stream) {
+    SEHIP_REQUIRE(S >= 1 && S <= PIT_MAXS, "pit_pointwise_bwd: S=%d outside [1, %d]", S, PIT_MAXS);
+    SEHIP_REQUIRE(mode == 0 || mode == 1, "pit_pointwise_bwd: mode=%d (0 = l1, 1 = mse)", mode);
+    SEHIP_REQUIRE(B > 0 && C > 0 && n > 0, "pit_pointwise_bwd: empty input (B=%d C=%d n=%d)", B, C, n);
+    SEHIP_REQUIRE((long)B * C <= PITPW_MAXROWS && n <= PITPW_MAXN, "pit_pointwise_bwd: shape too large (B*C=%ld n=%d)", (long)B * C, n);
+    SEHIP_REQUIRE(est && ref && perm && dest, "pit_pointwise_bwd: null pointer");
+    const bool vec = pitpw_vec(est, ref, dest, n);
+    int gy = cdiv(n, PITPW_THREADS * 8);
+    if (gy > 64) gy = 64;
+    const dim3 grid(B * C, gy, S);
+    const float scale = (float)(1.0 / ((double)S * B * C * n));
+    hipStream_t st = (hipStream_t)stream;
+#define PITPW_BWD(MODE_, VEC_) \
+    pit_pointwise_bwd_kernel<MODE_, VEC_><<<grid, PITPW_THREADS, 0, st>>>(est, ref, perm, upstream, S, C, n, scale, dest)
+    if (mode == 0) { if (vec) PITPW_BWD(0, true); else PITPW_BWD(0, false); }
+    else           { if (vec) PITPW_BWD(1, true); else PITPW_BWD(1, false); }
+#undef PITPW_BWD
+    SEHIP_CHECK_LAUNCH("pit_pointwise_bwd");
     return 0;
 }

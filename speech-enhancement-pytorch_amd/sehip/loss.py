@@ -69,11 +69,87 @@ def pit_loss_sisdr(enhance, target, return_comb=False):
     return (loss, perm) if return_comb else loss
 
 
+class _PitPointwiseLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, est, ref, mode, partials):
+        b, s = est.shape[0], est.shape[1]
+        n = est.shape[-1] if est.dim() >= 3 else 1
+        e4 = est.reshape(b, s, -1, n).contiguous().float()
+        r4 = ref.reshape(b, s, -1, n).contiguous().float()
+        loss, pairloss, perm = ops.pit_pointwise_fwd(e4, r4, mode, partials)
+        ctx.save_for_backward(e4, r4, perm)
+        ctx.mode, ctx.shape = mode, est.shape
+        ctx.mark_non_differentiable(perm, pairloss)
+        return loss.reshape(()), perm, pairloss
+
+    @staticmethod
+    def backward(ctx, g, _gp, _gl):
+        e4, r4, perm = ctx.saved_tensors
+        d = ops.pit_pointwise_bwd(e4, r4, perm, ctx.mode, g.reshape(1).contiguous().float())
+        return d.view(ctx.shape), None, None, None
+
+
+PIT_MAX_SPEAKERS = 6      # PIT_MAXS of csrc/loss.hip
+_pit_workspaces = {}      # (device, B, S, C, n) -> partials [blocks, S*S]: scratch of the pair-matrix kernel, consumed by the select kernel
+                          # of the same call on the same stream, so one buffer per shape serves every call (and exists before a capture)
+
+
+def pit_pointwise_workspace(shape, device):
+    """The cached pair-matrix workspace for enhance / target of `shape` [B, S, ..., n] on `device`.  pit_loss_pointwise fetches it
+    itself; a caller that records the loss into a hipGraph calls this BEFORE the capture begins, so the recording allocates nothing
+    but the call's own outputs."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    b, s = int(shape[0]), int(shape[1])
+    n = int(shape[-1]) if len(shape) >= 3 else 1
+    c = 1
+    for d in shape[2:-1]:
+        c *= int(d)
+    key = (device, b, s, c, n)
+    ws = _pit_workspaces.get(key)
+    if ws is None:
+        ws = torch.empty(ops.pit_pointwise_blocks(b, s, c, n), s * s, device=device, dtype=torch.float32)
+        if not (device.type == "cuda" and torch.cuda.is_current_stream_capturing()):
+            _pit_workspaces[key] = ws      # (a buffer born inside a capture lives in that graph's pool: it serves that recording only)
+    return ws
+
+
+def pit_loss_pointwise(enhance, target, mode, return_comb=False):
+    """UtterenceBaasedPermutationInvariantTraining(enhance, target, loss_function=l1_loss | mse_loss) of src/loss.py:58-100 on the
+    device (mode 'l1' / 0 or 'mse' / 1): enhance / target [B, S, ...], speakers on axis 1, S <= 6.  One pass over the data fills
+    the S x S matrix of batch-mean pair losses, a single wave picks the permutation (first minimum in itertools order, no gradient
+    through the choice) and the backward pass reads it from device memory: no host round trip, so the call can be recorded into a
+    hipGraph, and no atomics, so the bits do not depend on utils.set_deterministic.  With return_comb the device tensor perm [S]
+    int32 (perm[j] = estimated speaker matched with target j) is returned as well, as by pit_loss_sisdr."""
+    mode = {"l1": 0, "mse": 1}.get(mode, mode)
+    if mode not in (0, 1):
+        raise SehipError(f"pit_loss_pointwise: mode {mode!r} (expected 'l1' / 0 or 'mse' / 1)")
+    if enhance.shape != target.shape:
+        raise SehipError(f"enhance and target shape did not match...{tuple(enhance.shape)}, {tuple(target.shape)}")
+    if enhance.dim() < 2 or not 1 <= enhance.shape[1] <= PIT_MAX_SPEAKERS:
+        raise SehipError(f"pit_loss_pointwise: expected [batch, speakers <= {PIT_MAX_SPEAKERS}, ...], got {tuple(enhance.shape)}")
+    from ._lib import require_gpu
+    require_gpu(enhance, "pit_loss_pointwise")
+    loss, perm, _ = _PitPointwiseLoss.apply(enhance, target, mode, pit_pointwise_workspace(enhance.shape, enhance.device))
+    return (loss, perm) if return_comb else loss
+
+
 def pit_loss(enhance, target, loss_function, return_comb=False):
-    """The same for any loss function of this module.  si-sdr runs fused on the device; the other losses evaluate the S x S
-    pair matrix with S*S small launches and read it back once to pick the permutation (src/loss.py:67-86)."""
+    """The same for any loss function of this module.  si-sdr, l1 and mse run fused on the device without a host round trip (l1 / mse
+    for up to 6 speakers on the GPU: pit_loss_pointwise; return_comb then gives the reference's list of (ienhance, itarget) pairs,
+    built from the device permutation with one readback on that opt-in path only).  Any other loss function, or more than 6
+    speakers, evaluates the S x S pair matrix with S*S small launches and reads it back once to pick the permutation
+    (src/loss.py:67-86).  `psa` is not a PIT loss: the reference's own PIT raises for it (src/loss.py:95 calls the three-argument loss
+    with two arguments), so there is no behaviour to match."""
     if loss_function is loss_sisdr:
         return pit_loss_sisdr(enhance, target, return_comb)
+    if (loss_function is l1_loss or loss_function is mse_loss) and enhance.shape == target.shape and enhance.dim() >= 2 and \
+            1 <= enhance.shape[1] <= PIT_MAX_SPEAKERS and enhance.is_cuda and enhance.numel() > 0:
+        res = pit_loss_pointwise(enhance, target, 0 if loss_function is l1_loss else 1, return_comb)
+        if not return_comb:
+            return res
+        return res[0], [(i, j) for j, i in enumerate(res[1].cpu().tolist())]
     if enhance.shape != target.shape:
         raise SehipError(f"enhance and target shape did not match...{tuple(enhance.shape)}, {tuple(target.shape)}")
     from itertools import permutations

@@ -116,3 +116,33 @@ def sisnr_pit_bwd(est, ref, rowstat, perm, upstream=None):
     dest = torch.empty_like(est)
     call("sehip_sisnr_pit_bwd", ptr(est), ptr(ref), ptr(rowstat), ptr(perm), ptr(upstream), b, s, c, n, ptr(dest), stream())
     return dest
+
+
+def pit_pointwise_blocks(b, s, c, n):
+    """Records of the pair-matrix workspace for est / ref [B,S,C,N]: partials is [blocks, S*S] fp32."""
+    blocks = _lib.lib().sehip_pit_pointwise_blocks(b, s, c, n)
+    if blocks <= 0:
+        raise _lib.SehipError(f"pit_pointwise: bad shape (B={b} S={s} C={c} n={n}; 1 <= S <= 6, positive sizes)")
+    return blocks
+
+
+def pit_pointwise_fwd(est, ref, mode, partials=None):
+    """est/ref [B,S,C,N] fp32 contiguous, mode 0 = l1 / 1 = mse -> (loss [1], pairloss [S*S], perm [S] int32): the
+    permutation-invariant l1 / mse of src/loss.py:58-100 in one pass over the data.  partials [pit_pointwise_blocks(...), S*S]
+    fp32 is workspace (allocated here when None; pass a cached one to keep the call free of allocations)."""
+    require_gpu(est, "pit_pointwise_fwd")
+    b, s, c, n = est.shape
+    if partials is None:
+        partials = torch.empty(pit_pointwise_blocks(b, s, c, n), s * s, device=est.device, dtype=torch.float32)
+    pairloss = torch.empty(s * s, device=est.device, dtype=torch.float32)
+    perm = torch.empty(s, device=est.device, dtype=torch.int32)
+    loss = torch.empty(1, device=est.device, dtype=torch.float32)
+    call("sehip_pit_pointwise_fwd", ptr(est), ptr(ref), b, s, c, n, mode, ptr(partials), ptr(pairloss), ptr(perm), ptr(loss), stream())
+    return loss, pairloss, perm
+
+
+def pit_pointwise_bwd(est, ref, perm, mode, upstream=None):
+    b, s, c, n = est.shape
+    dest = torch.empty_like(est)
+    call("sehip_pit_pointwise_bwd", ptr(est), ptr(ref), ptr(perm), ptr(upstream), b, s, c, n, mode, ptr(dest), stream())
+    return dest

@@ -319,19 +319,25 @@ class Solver(object):
             mixture = mixture.unsqueeze(1).expand_as(sources)
         return self.loss_function(enhanced, sources, mixture)
 
+    def _pit_applies(self, sources):
+        return bool(_cfg(self.config.optim, "pit_apply", False)) and sources.dim() >= 3 and sources.shape[1] >= 2 and \
+            self.config.model.name in MULTI_SPEECH_SEPERATION_MODELS
+
+    def _step_loss(self, enhanced, sources, mixture):
+        """The loss of one train step, eager and captured alike.  The reference computes a PIT loss here and then overwrites it with the
+        plain loss (src/solver.py:469-480; its shipped config has optim.pit: True), so optim.pit alone changes nothing here either.
+        The opt-in optim.pit_apply keeps the permutation-invariant value (src/loss.py:58-100) for models that return
+        [batch, speakers, ...]."""
+        if self._pit_applies(sources):
+            from .loss import pit_loss
+            return pit_loss(enhanced, sources, self.loss_function)
+        return self._loss(enhanced, sources, mixture)
+
     def _train_step(self, mixture, sources):
         if not self.model.training:
             self.model.train()
         enhanced = self.model(mixture)
-        # The reference computes a PIT loss here and then overwrites it with the plain loss (src/solver.py:469-480; its shipped
-        # config has optim.pit: True), so optim.pit alone changes nothing here either.  The opt-in optim.pit_apply keeps the
-        # permutation-invariant value (src/loss.py:58-100) for models that return [batch, speakers, ...].
-        if _cfg(self.config.optim, "pit_apply", False) and sources.dim() >= 3 and sources.shape[1] >= 2 and \
-                self.config.model.name in MULTI_SPEECH_SEPERATION_MODELS:
-            from .loss import pit_loss
-            loss = pit_loss(enhanced, sources, self.loss_function)
-        else:
-            loss = self._loss(enhanced, sources, mixture)
+        loss = self._step_loss(enhanced, sources, mixture)
         self.optimizer.zero_grad()
         fused = isinstance(self.optimizer, FlatOptimizer)
         works, early_guard = [], False
@@ -419,11 +425,18 @@ class Solver(object):
         if self.model._anchor is None or self.model._anchor.device != mixture.device:
             self.model._anchor = torch.zeros(1, device=mixture.device, requires_grad=True)
         mix, src = mixture.clone(), sources.clone()
+        if self._pit_applies(src):
+            from . import loss as loss_module
+            if self.loss_function in (loss_module.l1_loss, loss_module.mse_loss) and src.shape[1] <= loss_module.PIT_MAX_SPEAKERS:
+                loss_module.pit_pointwise_workspace(src.shape, src.device)   # the pair-matrix workspace exists before the capture
+            elif self.loss_function is not loss_module.loss_sisdr:
+                raise SehipError("solver.use_graph with optim.pit_apply needs optim.loss si-sdr, l1 or mse and at most "
+                                 f"{loss_module.PIT_MAX_SPEAKERS} speakers: the permutation of any other loss is picked on the host")
         torch.cuda.synchronize()
         fb, upd = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
         with torch.cuda.graph(fb):
             enhanced = self.model(mix)
-            loss = self._loss(enhanced, src, mix)
+            loss = self._step_loss(enhanced, src, mix)
             self.optimizer.zero_grad()
             loss.backward()
             loss_out = loss.detach().clone()
