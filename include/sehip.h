@@ -79,6 +79,18 @@ int sehip_wav_row_stats(const float* raw, const long* row_off, int rows, float* 
 int sehip_wav_collate(const float* raw, const long* row_off, const int* out_row, const long* out_start, const int* out_valid,
                       const float* stats, int mode, float eps, int seg, int out_rows, float* out, void* stream);
 
+/* ---- julius.resample_frac in front of the data path (src/dataset.py:117-122, :354-359 resample every mixture and source before
+ *      the statistics and the crop).  old_sr / new_sr: the REDUCED ratio, both terms in [1, 1024]; width = ceil(24 * old / (0.945 *
+ *      min(old, new))); kernels [new_sr][2 * width + old_sr] fp32, one row per output phase, each of unit sum (sehip/ops.py:
+ *      resample_kernels).  Rows as for wav_row_stats: raw[row_off[r] .. row_off[r + 1]), starts unaligned.  Output row r =
+ *      out[out_off[r] .. out_off[r + 1]) holds sehip_resample_out_len(len_r) samples (possibly none); sample m = q * new_sr + p is
+ *          sum_{k < 2 * width + old_sr} kernels[p][k] * x[clamp(q * old_sr + k - width, 0, len_r - 1)]      (replicate padding),
+ *      fp32 throughout, one launch, bit-identical from run to run.  Arguments are validated before any HIP call.
+ *      resample_out_len: floor(n * new / old) (the ratio is reduced by its gcd inside), -1 for a non-positive term or n < 0. */
+long sehip_resample_out_len(long n, int old_sr, int new_sr);
+int sehip_resample_frac(const float* raw, const long* row_off, int rows, const float* kernels, int old_sr, int new_sr, int width,
+                        float* out, const long* out_off, void* stream);
+
 /* ---- SI-SNR loss: src/loss.py:14-29 (si_snr, loss_sisdr).  rowstat is [rows][4] fp32 scratch kept for bwd. */
 int sehip_sisnr_fwd(const float* est, const float* ref, int rows, int n, float* rowstat, float* loss, void* stream);
 /* SI-SDR validation metric of src/metric.py:92-123 (SI_SDR) on device rows [rows][n]: out[0] = 10 log10(mean ratio + eps);

@@ -50,6 +50,8 @@ _PROTOS = {
     "sehip_comm_destroy": [P],
     "sehip_wav_row_stats": [P, P, I, P, P],
     "sehip_wav_collate": [P, P, P, P, P, P, I, F, I, I, P, P],
+    "sehip_resample_out_len": [L, I, I],
+    "sehip_resample_frac": [P, P, I, P, I, I, I, P, P, P],
     "sehip_sisnr_fwd": [P, P, I, I, P, P, P],
     "sehip_sisdr_metric": [P, P, I, I, P, P, P],
     "sehip_sisnr_bwd": [P, P, P, P, I, I, P, P],
@@ -189,7 +191,7 @@ _PROTOS = {
     "sehip_wun_out_fwd": [P, P, P, P, L, I, P, P],
     "sehip_wun_out_bwd": [P, P, P, P, P, L, I, P, P, P, P, P],
 }
-_RESTYPE = {"sehip_wun_bn_scratch_floats": C.c_long, "sehip_wun_enc0_wgrad_scratch_floats": C.c_long, "sehip_wun_out_bwd_scratch_floats": C.c_long,
+_RESTYPE = {"sehip_resample_out_len": C.c_long, "sehip_wun_bn_scratch_floats": C.c_long, "sehip_wun_enc0_wgrad_scratch_floats": C.c_long, "sehip_wun_out_bwd_scratch_floats": C.c_long,
             "sehip_lstm2_gran_bytes": C.c_long, "sehip_dmx_attn_bwd_scratch_floats": C.c_long, "sehip_ctn_codec_bwd_scratch_floats": C.c_long, "sehip_ctn_gln_bwd_scratch_floats": C.c_long, "sehip_ctn_cln_bwd_scratch_floats": C.c_long, "sehip_wgrad_group_bytes": C.c_long, "sehip_wgrad_dense_group_bytes": C.c_long, "sehip_cbn_scratch_floats": C.c_long, "sehip_rbn_scratch_floats": C.c_long, "sehip_dcunet_tail_scratch_floats": C.c_long, "sehip_event_create": C.c_void_p, "sehip_stream_create": C.c_void_p}
 
 

@@ -9,12 +9,21 @@ the host), moves them to the GPU as one flat buffer and builds the reference's b
     batcher = DeviceBatcher(config.dset, normalize="z-score", sample_length=64000, drop_last=True)
     mixture, sources, mix_meta, src_meta, names, index_batch = batcher(items)      # items: [(mixture [C, n], sources [S, C, n], name)]
 
+Files that are not at config.sample_rate (VoiceBank-DEMAND is 48 kHz, Clarity 44.1 kHz, both trained at 16 kHz) go through
+julius.resample_frac in the reference BEFORE the statistics, the normalisation and the crop (src/dataset.py:117-122, :354-359).
+`batcher(items, rates=48000)` (or one rate per utterance, what sf.read reported) does that on the device too: csrc/resample.hip
+writes the resampled rows into a second flat buffer, one launch per distinct ratio, and the two kernels above run on that buffer;
+crop offsets, segment counts and statistics all follow the RESAMPLED length floor(n * new / old).
+
 The tuple is the one `for batch in dataloader` yields in src/solver.py:430-441; `Solver._run_one_epoch` consumes it unchanged.
 The crop offsets come from numpy's global RNG in the reference's order (one np.random.randint per utterance), so a seeded run
 crops where the reference crops."""
+import math
+
 import numpy as np
 import torch
 
+from . import ops
 from ._lib import SehipError, call, ptr, stream, require_gpu
 
 _MODES = {"": 0, None: 0, "none": 0, "z-score": 1, "linear-scale": 2}
@@ -44,6 +53,7 @@ class DeviceBatcher:
         if normalize not in _MODES:
             raise SehipError(f"DeviceBatcher: normalize must be one of {[k for k in _MODES if k]}, got {normalize!r}")
         self.seg = int(config.segment * config.sample_rate)
+        self.sample_rate = int(config.sample_rate)
         self.mode, self.sample_length, self.drop_last = _MODES[normalize], int(sample_length or 0), bool(drop_last)
         self.device = torch.device(device)
         self.rng = rng if rng is not None else np.random
@@ -56,7 +66,43 @@ class DeviceBatcher:
             return [0] * len(lengths)
         return [int(self.rng.randint(max(n, self.sample_length) - self.sample_length + 1)) for n in lengths]
 
-    def __call__(self, items, starts=None):
+    def resampled_lengths(self, lengths, rates):
+        """floor(n * sample_rate / rate) per utterance: what julius.resample_frac leaves of n samples read at `rate`
+        (rates: None, one int, or one int per utterance)."""
+        if rates is None:
+            return [int(n) for n in lengths]
+        if isinstance(rates, (int, np.integer)):
+            rates = [rates] * len(lengths)
+        rates = [int(r) for r in rates]
+        if len(rates) != len(lengths) or any(r <= 0 for r in rates):
+            raise SehipError(f"DeviceBatcher: rates must be one positive int, or one per utterance ({len(lengths)}), got {rates}")
+        out = []
+        for n, r in zip(lengths, rates):
+            g = math.gcd(r, self.sample_rate)
+            out.append(int(n) * (self.sample_rate // g) // (r // g))
+            if r != self.sample_rate and out[-1] == 0:
+                raise SehipError(f"DeviceBatcher: {n} samples at {r} Hz leave nothing at {self.sample_rate} Hz")
+        return out
+
+    def _resample(self, raw, raw_off, rs_off, rates, rpi, d_rs_off):
+        """raw (rows at raw_off, utterances sorted by rate) -> the second flat buffer (rows at rs_off): one resampler launch per
+        distinct ratio, a device copy for the run that is already at the target rate."""
+        d_raw_off = torch.from_numpy(raw_off).to(raw.device)
+        out = torch.empty(int(rs_off[-1]), dtype=torch.float32, device=raw.device)
+        u = 0
+        while u < len(rates):
+            v = u
+            while v < len(rates) and rates[v] == rates[u]:
+                v += 1
+            r0, r1 = u * rpi, v * rpi
+            if rates[u] == self.sample_rate:
+                out[int(rs_off[r0]):int(rs_off[r1])].copy_(raw[int(raw_off[r0]):int(raw_off[r1])])
+            else:
+                ops.resample_rows(raw, d_raw_off[r0:r1 + 1], r1 - r0, rates[u], self.sample_rate, out, d_rs_off[r0:r1 + 1])
+            u = v
+        return out
+
+    def __call__(self, items, starts=None, rates=None):
         if not items:
             raise SehipError("DeviceBatcher: empty batch")
         mixes = [torch.as_tensor(it[0], dtype=torch.float32) for it in items]
@@ -66,7 +112,12 @@ class DeviceBatcher:
         for m, s_ in zip(mixes, srcs):
             if m.dim() != 2 or s_.dim() != 3 or m.shape[0] != C or tuple(s_.shape[:2]) != (S, C) or s_.shape[-1] != m.shape[-1]:
                 raise SehipError(f"DeviceBatcher: mixture [C, n] / sources [S, C, n] expected, got {tuple(m.shape)} / {tuple(s_.shape)}")
-        lengths = [int(m.shape[-1]) for m in mixes]
+        raw_lengths = [int(m.shape[-1]) for m in mixes]
+        lengths = self.resampled_lengths(raw_lengths, rates)       # everything below the resampler sees the resampled utterance
+        if rates is None or isinstance(rates, (int, np.integer)):
+            rates = [self.sample_rate if rates is None else int(rates)] * len(items)
+        rates = [int(r) for r in rates]
+        resample = any(r != self.sample_rate for r in rates)
         if starts is None:
             starts = self.draw_starts(lengths)
         plan = plan_batch(lengths, self.seg, self.sample_length, self.drop_last, starts)
@@ -75,11 +126,21 @@ class DeviceBatcher:
             raise SehipError("DeviceBatcher: no segment survives drop_last")
         rpi = C + S * C                                             # raw rows per utterance: mixture channels, then (source, channel)
         R = len(items) * rpi
-        row_off = np.zeros(R + 1, dtype=np.int64)
-        row_off[1:] = np.cumsum(np.repeat(lengths, rpi))
-        flat = torch.empty(int(row_off[-1]), dtype=torch.float32).pin_memory() if torch.cuda.is_available() else torch.empty(int(row_off[-1]))
+        # the utterances lie in the flat buffers grouped by rate, so that each distinct ratio is ONE run of rows (one launch);
+        # without resampling this is the batch order
+        order = sorted(range(len(items)), key=lambda i: rates[i]) if resample else list(range(len(items)))
+        pos = [0] * len(items)
+        for j, i in enumerate(order):
+            pos[i] = j
+        raw_off = np.zeros(R + 1, dtype=np.int64)
+        raw_off[1:] = np.cumsum(np.repeat([raw_lengths[i] for i in order], rpi))
+        row_off = raw_off
+        if resample:
+            row_off = np.zeros(R + 1, dtype=np.int64)
+            row_off[1:] = np.cumsum(np.repeat([lengths[i] for i in order], rpi))
+        flat = torch.empty(int(raw_off[-1]), dtype=torch.float32).pin_memory() if torch.cuda.is_available() else torch.empty(int(raw_off[-1]))
         for i, (m, s_) in enumerate(zip(mixes, srcs)):
-            n, b0 = lengths[i], int(row_off[i * rpi])
+            n, b0 = raw_lengths[i], int(raw_off[pos[i] * rpi])
             flat[b0:b0 + C * n].view(C, n).copy_(m)
             flat[b0 + C * n:b0 + rpi * n].view(S, C, n).copy_(s_)
         # output rows: mixture [G, C, seg] first, then sources [G, S, C, seg]
@@ -92,16 +153,18 @@ class DeviceBatcher:
             for k in range(nseg):
                 v = max(0, min(self.seg, valid - k * self.seg))
                 a = (g + k) * C
-                out_row[a:a + C] = i * rpi + np.arange(C)
+                out_row[a:a + C] = pos[i] * rpi + np.arange(C)
                 out_start[a:a + C], out_valid[a:a + C] = st + k * self.seg, v
                 b_ = n_mix + (g + k) * S * C
-                out_row[b_:b_ + S * C] = i * rpi + C + np.arange(S * C)
+                out_row[b_:b_ + S * C] = pos[i] * rpi + C + np.arange(S * C)
                 out_start[b_:b_ + S * C], out_valid[b_:b_ + S * C] = st + k * self.seg, v
             g += nseg
         dev = self.device
         require_gpu(torch.empty(0, device=dev), "DeviceBatcher")
         raw = flat.to(dev, non_blocking=True)
         d_off = torch.from_numpy(row_off).to(dev)
+        if resample:
+            raw = self._resample(raw, raw_off, row_off, [rates[i] for i in order], rpi, d_off)
         stats = torch.zeros(R, 4, dtype=torch.float32, device=dev)
         if self.mode:
             call("sehip_wav_row_stats", ptr(raw), ptr(d_off), R, ptr(stats), stream())
@@ -115,8 +178,8 @@ class DeviceBatcher:
         zero = 0
         mix_meta, src_meta = [], []
         for i in range(len(items)):          # the reference's per-utterance dictionaries (src/dataset.py:131-143), values on the device
-            sm = stats[i * rpi:i * rpi + C]
-            ss = stats[i * rpi + C:(i + 1) * rpi].view(S, C, 4)
+            sm = stats[pos[i] * rpi:pos[i] * rpi + C]
+            ss = stats[pos[i] * rpi + C:(pos[i] + 1) * rpi].view(S, C, 4)
             if self.mode == 1:
                 mix_meta.append({"min": zero, "max": zero, "mean": sm[:, 0:1], "std": sm[:, 1:2]})
                 src_meta.append({"min": zero, "max": zero, "mean": ss[..., 0:1], "std": ss[..., 1:2]})

@@ -146,3 +146,85 @@ def pit_pointwise_bwd(est, ref, perm, mode, upstream=None):
     dest = torch.empty_like(est)
     call("sehip_pit_pointwise_bwd", ptr(est), ptr(ref), ptr(perm), ptr(upstream), b, s, c, n, mode, ptr(dest), stream())
     return dest
+
+
+# ---- julius.resample_frac (julius 0.2.7 ResampleFrac with its defaults), csrc/resample.hip -------------------------------------
+RESAMPLE_ZEROS, RESAMPLE_ROLLOFF = 24, 0.945
+_resample_tables = {}      # (reduced old, reduced new, device) -> (table, width, old, new)
+
+
+def resample_out_len(n, old_sr, new_sr):
+    """floor(n * new_sr / old_sr): the length julius.resample_frac returns for n samples."""
+    m = _lib.lib().sehip_resample_out_len(int(n), int(old_sr), int(new_sr))
+    if m < 0:
+        raise _lib.SehipError(f"resample: bad length / ratio (n={n}, {old_sr} -> {new_sr})")
+    return int(m)
+
+
+def resample_kernels(old_sr, new_sr, device="cpu"):
+    """-> (table fp32 [new][2 * width + old], width, old, new) with old / new the reduced ratio: the windowed-sinc interpolation
+    kernels of julius's ResampleFrac (zeros=24, rolloff=0.945, squared-cosine window, each phase normalised to unit sum), built on
+    the host in float32 torch arithmetic and cached per reduced ratio and device."""
+    old_sr, new_sr = int(old_sr), int(new_sr)
+    if old_sr <= 0 or new_sr <= 0:
+        raise _lib.SehipError(f"resample_kernels: sample rates must be positive, got {old_sr} -> {new_sr}")
+    g = int(np.gcd(old_sr, new_sr))
+    old, new = old_sr // g, new_sr // g
+    device = torch.device(device)
+    key = (old, new, str(device))
+    hit = _resample_tables.get(key)
+    if hit is not None:
+        return hit
+    host = _resample_tables.get((old, new, "cpu"))
+    if host is None:
+        sr = min(new, old) * RESAMPLE_ROLLOFF
+        width = int(np.ceil(RESAMPLE_ZEROS * old / sr))
+        idx = torch.arange(-width, width + old, dtype=torch.float32)
+        rows = []
+        for i in range(new):
+            t = (-i / new + idx / old) * sr
+            t = t.clamp(-RESAMPLE_ZEROS, RESAMPLE_ZEROS) * np.pi
+            window = torch.cos(t / RESAMPLE_ZEROS / 2) ** 2
+            one = torch.ones_like(t)
+            k = torch.where(t == 0, one, torch.sin(t) / torch.where(t == 0, one, t)) * window
+            rows.append(k / k.sum())
+        host = (torch.stack(rows).contiguous(), width, old, new)
+        _resample_tables[(old, new, "cpu")] = host
+    if device.type != "cpu":
+        host = (host[0].to(device), host[1], old, new)
+        _resample_tables[key] = host
+    return host
+
+
+def resample_rows(raw, row_off, rows, old_sr, new_sr, out, out_off):
+    """The flat-buffer call: `rows` rows raw[row_off[r] .. row_off[r + 1]) (device fp32 / int64) are written to
+    out[out_off[r] .. out_off[r + 1]), floor(len * new / old) samples each; the caller sizes out / out_off (resample_out_len)."""
+    require_gpu(raw, "resample_rows")
+    table, width, old, new = resample_kernels(old_sr, new_sr, raw.device)
+    call("sehip_resample_frac", ptr(raw), ptr(row_off), int(rows), ptr(table), old, new, width, ptr(out), ptr(out_off), stream())
+    return out
+
+
+def resample_frac(x, old_sr, new_sr):
+    """julius.resample_frac(x, old_sr, new_sr) (output_length=None, full=False: what src/dataset.py uses) for a CUDA fp32 tensor
+    [..., T] -> [..., floor(T * new / old)]."""
+    if int(old_sr) == int(new_sr):
+        return x
+    if not torch.is_tensor(x) or not x.is_cuda:
+        raise _lib.SehipError(f"resample_frac: needs a CUDA tensor (got {getattr(x, 'device', type(x))}); there is no CPU fallback")
+    if x.dtype != torch.float32:
+        raise _lib.SehipError(f"resample_frac: fp32 only, got {x.dtype}")
+    if x.dim() < 1 or x.shape[-1] == 0:
+        raise _lib.SehipError(f"resample_frac: needs at least one sample along the last axis, got shape {tuple(x.shape)}")
+    T = int(x.shape[-1])
+    rows = x.numel() // T
+    m = resample_out_len(T, old_sr, new_sr)
+    out = torch.empty(*x.shape[:-1], m, dtype=torch.float32, device=x.device)
+    if rows == 0 or m == 0:
+        return out
+    xc = x.contiguous()
+    row_off = torch.arange(rows + 1, dtype=torch.int64, device=x.device) * T
+    out_off = torch.arange(rows + 1, dtype=torch.int64, device=x.device) * m
+    table, width, old, new = resample_kernels(old_sr, new_sr, x.device)
+    call("sehip_resample_frac", ptr(xc), ptr(row_off), rows, ptr(table), old, new, width, ptr(out), ptr(out_off), stream())
+    return out
