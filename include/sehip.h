@@ -733,6 +733,54 @@ int sehip_wun_out_fwd(const void* z, const float* x, const float* W, const float
 int sehip_wun_out_bwd(const float* dout, const float* out, const void* z, const float* x, const float* W, long rows, int C0, void* dz,
                       float* dW, float* db, float* scratch, void* stream);
 
+/* ---- rnn-stft-mask (src/model/stft_rnn.py:5-119, RNNBaseSTFTMask; csrc/rnnmask.hip).  The reference runs its nn.LSTM / nn.GRU with
+ *      batch_first=False on [B C][T][F]: the recurrence walks the L = B C axis and the T frames are its independent rows.  Activations
+ *      are bf16 [T][L][channels] (row r = t L + l), channel axes padded to a multiple of 8 with zeros; gate pre-activations, activated
+ *      gates and the carried state are fp32.  D = 1 or 2 directions, H a multiple of 32 up to 1024.  No atomics: every sum has one
+ *      owner and a fixed order.
+ *      counter_next  : used[0] (uint32) = low word of counter[0] (uint64); counter[0] += 1 -- the dropout step counter, on the device
+ *      features      : feat [T][RC][Fp] bf16 = |re^2 - im^2| of x [RC][F][T][2] fp32 (:112-119: not a magnitude), columns F .. Fp-1 zero
+ *      pack_w        : bf16 copy of a weight w fp32 [N][K]: dst [N][ld] (zeros from K to the next multiple of 8) or, transpose != 0,
+ *                      dst [K][ld] (zeros from N to the next multiple of 8)
+ *      gemm_nt       : C [M][ldc] = A [M][lda] B [N][ldb]^T over K columns (bf16 operands, K, lda, ldb multiples of 8).  epilogue 0: C
+ *                      fp32; 1: C bf16; 2: C bf16 = max(. + bias[n], 0) (the head's Linear + ReLU)
+ *      gemm_tn       : dW [N][ldw] fp32 = sum_m A[m][0..N)^T X[m + shift][0..K), rows paired only inside a run of L rows (M % L == 0;
+ *                      shift 0 with any L: plain).  ldw is the parameter's own row length: gradients land in its layout, unpadded
+ *      rnn_fwd       : one layer, L launches.  pre fp32 [Bn][L][D][G][H] = x W_ih^T (G = 4: i, f, g, o; gru: 3: r, z, n), whh bf16
+ *                      [D][G H][H]; writes gates fp32 [Bn][L][D][4][H] (LSTM: activated i, f, g, o; GRU: r, z, n, (W_hn h)), hs bf16
+ *                      [Bn][L][D H], state fp32 [Bn][L][D H] (LSTM: c; GRU: h), and with hd != NULL hd bf16 [Bn][L][D H] = hs after
+ *                      dropout: kept when (mix(mix(index ^ key) + 0x9e3779b9) >> 8) >= thresh, key = mix(seed_lo ^ mix(seed_hi ^
+ *                      mix(ctr[0] 0x9e3779b9 + layer))), mix = the 32-bit murmur3 finaliser, scaled by `scale`
+ *      rnn_bwd       : dhs bf16 [Bn][L][D H] = gradient of hs (of hd when thresh != 0: the same mask is regenerated); writes dG bf16
+ *                      [Bn][L][D][4][H] (LSTM: pre-activation gradients; GRU: (d pre_r, d pre_z, d pre_n, r d pre_n): blocks 0..2
+ *                      belong to x W_ih^T, blocks 0, 1, 3 to h W_hh^T); whhT bf16 [D][H][G H]; carry fp32 [D][Bn][H] scratch
+ *      colsum / colsum_finalize : per-column sums of a bf16 [rows][lda] in two fixed-order stages (part: sum_scratch_floats()).
+ *                      With y, coef: also sum a xhat, xhat = (y - mean) rstd.  finalize: out0 = sum a, out1 = sum a xhat (optional),
+ *                      bcoef [C][4] = (gamma rstd, out0 / rows, out1 / rows, 0) (optional) -- dbeta, dgamma and the head's bias gradient
+ *      bn_apply      : z = scale y + shift with coef [C][4] of sehip_wun_bn_finalize (BatchNorm1d without an activation)
+ *      bn_bwd_apply  : dy = gamma rstd (dz - mean(dz) - xhat mean(dz xhat))
+ *      mask_fwd      : out fp32 [B][S][C][F][T][2] = mask[(t, b C + c)][s F + f] x[b][c][f][t][:], mask bf16 [T][B C][SFp]
+ *      mask_bwd      : dpre bf16 [T][B C][SFp] = (mask > 0) (dout_re x_re + dout_im x_im); columns S F .. SFp-1 are not touched */
+long sehip_rsm_sum_scratch_floats(long rows, int C);
+int sehip_rsm_counter_next(void* counter, void* used, void* stream);
+int sehip_rsm_features(const float* x, int RC, int F, int T, int Fp, void* feat, void* stream);
+int sehip_rsm_pack_w(const float* w, int N, int K, int transpose, int ld, void* dst, void* stream);
+int sehip_rsm_gemm_nt(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epilogue, const float* bias, void* C, int ldc,
+                      void* stream);
+int sehip_rsm_gemm_tn(const void* A, int lda, const void* X, int ldx, int M, int N, int K, int L, int shift, float* dW, int ldw, void* stream);
+int sehip_rsm_rnn_fwd(int gru, const float* pre, const void* whh, float* gates, void* hs, float* state, void* hd, int Bn, int L, int H, int D,
+                      unsigned seed_lo, unsigned seed_hi, const void* ctr, int layer, unsigned thresh, float scale, void* stream);
+int sehip_rsm_rnn_bwd(int gru, const float* gates, const void* whhT, const float* state, const void* dhs, void* dG, float* carry, int Bn, int L,
+                      int H, int D, unsigned seed_lo, unsigned seed_hi, const void* ctr, int layer, unsigned thresh, float scale, void* stream);
+int sehip_rsm_colsum(const void* a, int lda, const void* y, const float* coef, long rows, int C, float* part, void* stream);
+int sehip_rsm_colsum_finalize(const float* part, long rows, int C, const float* gamma, const float* coef, float* out0, float* out1,
+                              float* bcoef, void* stream);
+int sehip_rsm_bn_apply(const void* y, const float* coef, long rows, int C, void* z, void* stream);
+int sehip_rsm_bn_bwd_apply(const void* dz, const void* y, const float* coef, const float* bcoef, long rows, int C, void* dy, void* stream);
+int sehip_rsm_mask_fwd(const void* mask, const float* x, int B, int Cn, int S, int F, int T, int SFp, float* out, void* stream);
+int sehip_rsm_mask_bwd(const float* dout, const float* x, const void* mask, int B, int Cn, int S, int F, int T, int SFp, void* dpre,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

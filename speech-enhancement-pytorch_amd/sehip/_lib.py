@@ -190,8 +190,22 @@ _PROTOS = {
     "sehip_wun_bn_bwd_apply": [P, P, P, P, P, L, I, P, P],
     "sehip_wun_out_fwd": [P, P, P, P, L, I, P, P],
     "sehip_wun_out_bwd": [P, P, P, P, P, L, I, P, P, P, P, P],
+    "sehip_rsm_sum_scratch_floats": [L, I],
+    "sehip_rsm_counter_next": [P, P, P],
+    "sehip_rsm_features": [P, I, I, I, I, P, P],
+    "sehip_rsm_pack_w": [P, I, I, I, I, P, P],
+    "sehip_rsm_gemm_nt": [P, I, P, I, I, I, I, I, P, P, I, P],
+    "sehip_rsm_gemm_tn": [P, I, P, I, I, I, I, I, I, P, I, P],
+    "sehip_rsm_rnn_fwd": [I, P, P, P, P, P, P, I, I, I, I, U, U, P, I, U, F, P],
+    "sehip_rsm_rnn_bwd": [I, P, P, P, P, P, P, I, I, I, I, U, U, P, I, U, F, P],
+    "sehip_rsm_colsum": [P, I, P, P, L, I, P, P],
+    "sehip_rsm_colsum_finalize": [P, L, I, P, P, P, P, P, P],
+    "sehip_rsm_bn_apply": [P, P, L, I, P, P],
+    "sehip_rsm_bn_bwd_apply": [P, P, P, P, L, I, P, P],
+    "sehip_rsm_mask_fwd": [P, P, I, I, I, I, I, I, P, P],
+    "sehip_rsm_mask_bwd": [P, P, P, I, I, I, I, I, I, P, P],
 }
-_RESTYPE = {"sehip_resample_out_len": C.c_long, "sehip_wun_bn_scratch_floats": C.c_long, "sehip_wun_enc0_wgrad_scratch_floats": C.c_long, "sehip_wun_out_bwd_scratch_floats": C.c_long,
+_RESTYPE = {"sehip_resample_out_len": C.c_long, "sehip_rsm_sum_scratch_floats": C.c_long, "sehip_wun_bn_scratch_floats": C.c_long, "sehip_wun_enc0_wgrad_scratch_floats": C.c_long, "sehip_wun_out_bwd_scratch_floats": C.c_long,
             "sehip_lstm2_gran_bytes": C.c_long, "sehip_dmx_attn_bwd_scratch_floats": C.c_long, "sehip_ctn_codec_bwd_scratch_floats": C.c_long, "sehip_ctn_gln_bwd_scratch_floats": C.c_long, "sehip_ctn_cln_bwd_scratch_floats": C.c_long, "sehip_wgrad_group_bytes": C.c_long, "sehip_wgrad_dense_group_bytes": C.c_long, "sehip_cbn_scratch_floats": C.c_long, "sehip_rbn_scratch_floats": C.c_long, "sehip_dcunet_tail_scratch_floats": C.c_long, "sehip_event_create": C.c_void_p, "sehip_stream_create": C.c_void_p}
 
 

@@ -69,13 +69,30 @@ def pit_loss_sisdr(enhance, target, return_comb=False):
     return (loss, perm) if return_comb else loss
 
 
+PIT_POINTWISE_MAX_ROWS = 1 << 20      # PITPW_MAXROWS of csrc/loss.hip: B * C, the pair-matrix kernel's grid extent
+
+
+def _pit_pointwise_view(shape):
+    """(B, S, C, n) the pair-matrix kernel sees for enhance / target [B, S, ..., n]: the last axis is a row's samples and the axes
+    between are its rows.  A tensor with more rows than the kernel's grid takes (an STFT-domain estimate [B, S, C, F, T, 2] at the
+    shipped size has B C F T rows of 2 samples) is ONE row per (batch, speaker) instead: the terms are element-wise and every
+    pair loss is a batch mean, so the grouping changes no value, only which shapes are taken."""
+    b, s = int(shape[0]), int(shape[1])
+    n = int(shape[-1]) if len(shape) >= 3 else 1
+    c = 1
+    for d in shape[2:-1]:
+        c *= int(d)
+    if b * c > PIT_POINTWISE_MAX_ROWS:
+        c, n = 1, c * n
+    return b, s, c, n
+
+
 class _PitPointwiseLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, est, ref, mode, partials):
-        b, s = est.shape[0], est.shape[1]
-        n = est.shape[-1] if est.dim() >= 3 else 1
-        e4 = est.reshape(b, s, -1, n).contiguous().float()
-        r4 = ref.reshape(b, s, -1, n).contiguous().float()
+        b, s, c, n = _pit_pointwise_view(est.shape)
+        e4 = est.reshape(b, s, c, n).contiguous().float()
+        r4 = ref.reshape(b, s, c, n).contiguous().float()
         loss, pairloss, perm = ops.pit_pointwise_fwd(e4, r4, mode, partials)
         ctx.save_for_backward(e4, r4, perm)
         ctx.mode, ctx.shape = mode, est.shape
@@ -101,11 +118,7 @@ def pit_pointwise_workspace(shape, device):
     device = torch.device(device)
     if device.type == "cuda" and device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
-    b, s = int(shape[0]), int(shape[1])
-    n = int(shape[-1]) if len(shape) >= 3 else 1
-    c = 1
-    for d in shape[2:-1]:
-        c *= int(d)
+    b, s, c, n = _pit_pointwise_view(shape)
     key = (device, b, s, c, n)
     ws = _pit_workspaces.get(key)
     if ws is None:
