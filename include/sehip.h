@@ -781,6 +781,41 @@ int sehip_rsm_mask_fwd(const void* mask, const float* x, int B, int Cn, int S, i
 int sehip_rsm_mask_bwd(const float* dout, const float* x, const void* mask, int B, int Cn, int S, int F, int T, int SFp, void* dpre,
                        void* stream);
 
+/* ---- hearing-aid back end (src/audio.py:33-61 amplify_torch = NAL-R FIR, compressor, tanh; csrc/hearing_aid.hip).  All rows are
+ *      dense fp32 [rows][n], 1 <= rows <= 65535, 1 <= n <= 2^30; arguments are validated before any HIP call; nothing synchronises,
+ *      reads back or uses atomics, no workgroup waits on another: every entry is capturable into a hipGraph and gives the same
+ *      bits from run to run, with and without sehip_set_deterministic.  sehip_last_kernel reports `tile=` (outputs / samples per
+ *      workgroup) and `tiles=` (per row) of the call.
+ *
+ *  FIR (src/ha/amplifier.py:206-215 conv1d(wav, nalr, padding = nfir) with the stored, reversed taps = a convolution with h):
+ *      taps [F][K] fp32 in h order (NOT reversed), K = nfir + 1 in [1, 1025]; row_set [rows] int32 on the device picks the tap set
+ *      of each row (NULL: set 0 for every row; an index outside [0, F) is clamped).  No workspace.
+ *        sehip_ha_fir_fwd: x [rows][n] -> out [rows][n + K - 1],  out[r][m] = sum_{k < K} h[f_r][k] * x[r][m - k], zero outside the row
+ *        sehip_ha_fir_adj: dout [rows][n + K - 1] -> dx [rows][n], dx[r][i]  = sum_{k < K} h[f_r][k] * dout[r][i + k]
+ *      (n is the length of x / dx in both.)  fp32 FMA, every output one chain over k = 0 .. K - 1 from 0: a row's bits do not
+ *      depend on the launch geometry or on the other rows.
+ *
+ *  Compressor (src/ha/compressor.py:73-109, the sample-by-sample host loop, as a scan), W = int(rms_buffer_size * fs) >= 1:
+ *        lv_i = sqrt(mean(z^2 over the W samples ending at i, zeros before the row) + 1e-8)
+ *        (a, b)_i = lv_i > threshold ? (1 - attack, attack * (lv_i * attenuation + (1 - attenuation) * threshold))
+ *                                    : (1 - release, release)
+ *        c_i = a_i * c_{i-1} + b_i, c_{-1} = 1;  gain[r][i] = fp32(c_i);  out[r][i] = z[r][i] * gain[r][i], tanh of it if soft_clip
+ *      attack / release are the per-sample coefficients 1 / (t_msec / 1000) / fs.  Levels, the window sums (a difference of two
+ *      prefix sums) and the compositions of the affine maps are float64; z, gain, out [rows][n] fp32 (gain is kept for the backward
+ *      pass).  ws: sehip_ha_compressor_ws_doubles(rows, n, W) DOUBLES of workspace (the prefix sums [rows][n] and five per-tile
+ *      arrays); the helper is host-only and returns 0 for an invalid shape or W < 1.  Six launches: tile sums, row scan, prefix,
+ *      tile maps, row scan, rescan.
+ *        sehip_ha_compressor_bwd: dz[i] = dout[i] * (1 - out[i]^2) * gain[i]  (dout[i] * gain[i] without soft_clip), count = rows * n
+ *      elements: the gain is a constant of the backward pass, as in the reference (rebuilt there from a detached array). */
+int sehip_ha_fir_fwd(const float* x, long rows, long n, const float* taps, int F, int K, const int* row_set /*or NULL*/, float* out,
+                     void* stream);
+int sehip_ha_fir_adj(const float* dout, long rows, long n, const float* taps, int F, int K, const int* row_set /*or NULL*/, float* dx,
+                     void* stream);
+long sehip_ha_compressor_ws_doubles(long rows, long n, int W);
+int sehip_ha_compressor_fwd(const float* z, long rows, long n, int W, double threshold, double attack, double release,
+                            double attenuation, int soft_clip, double* ws, float* gain, float* out, void* stream);
+int sehip_ha_compressor_bwd(const float* dout, const float* out, const float* gain, long count, int soft_clip, float* dz, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

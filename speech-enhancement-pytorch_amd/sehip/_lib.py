@@ -24,6 +24,7 @@ I = C.c_int
 L = C.c_long
 F = C.c_float
 U = C.c_uint
+D = C.c_double
 
 # name -> argtypes (all return int status unless listed in _RESTYPE)
 _PROTOS = {
@@ -204,8 +205,13 @@ _PROTOS = {
     "sehip_rsm_bn_bwd_apply": [P, P, P, P, L, I, P, P],
     "sehip_rsm_mask_fwd": [P, P, I, I, I, I, I, I, P, P],
     "sehip_rsm_mask_bwd": [P, P, P, I, I, I, I, I, I, P, P],
+    "sehip_ha_fir_fwd": [P, L, L, P, I, I, P, P, P],
+    "sehip_ha_fir_adj": [P, L, L, P, I, I, P, P, P],
+    "sehip_ha_compressor_ws_doubles": [L, L, I],
+    "sehip_ha_compressor_fwd": [P, L, L, I, D, D, D, D, I, P, P, P, P],
+    "sehip_ha_compressor_bwd": [P, P, P, L, I, P, P],
 }
-_RESTYPE = {"sehip_resample_out_len": C.c_long, "sehip_rsm_sum_scratch_floats": C.c_long, "sehip_wun_bn_scratch_floats": C.c_long, "sehip_wun_enc0_wgrad_scratch_floats": C.c_long, "sehip_wun_out_bwd_scratch_floats": C.c_long,
+_RESTYPE = {"sehip_resample_out_len": C.c_long, "sehip_ha_compressor_ws_doubles": C.c_long, "sehip_rsm_sum_scratch_floats": C.c_long, "sehip_wun_bn_scratch_floats": C.c_long, "sehip_wun_enc0_wgrad_scratch_floats": C.c_long, "sehip_wun_out_bwd_scratch_floats": C.c_long,
             "sehip_lstm2_gran_bytes": C.c_long, "sehip_dmx_attn_bwd_scratch_floats": C.c_long, "sehip_ctn_codec_bwd_scratch_floats": C.c_long, "sehip_ctn_gln_bwd_scratch_floats": C.c_long, "sehip_ctn_cln_bwd_scratch_floats": C.c_long, "sehip_wgrad_group_bytes": C.c_long, "sehip_wgrad_dense_group_bytes": C.c_long, "sehip_cbn_scratch_floats": C.c_long, "sehip_rbn_scratch_floats": C.c_long, "sehip_dcunet_tail_scratch_floats": C.c_long, "sehip_event_create": C.c_void_p, "sehip_stream_create": C.c_void_p}
 
 
