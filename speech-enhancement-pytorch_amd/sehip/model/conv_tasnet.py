@@ -17,46 +17,20 @@ from .. import plan_tasnet as P
 from .._lib import SehipError
 from .flat import FlatModule
 
-_STATIC_CACHE = {}
-
-
-class _TasNetFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, model, wav, anchor):
-        ctx.model = model
-        ctx.ws = model._run_forward(wav)
-        ctx.generation = ctx.ws.generation
-        return ctx.ws.out.clone()
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        if ctx.generation != ctx.ws.generation or ctx.ws.closed:
-            raise SehipError("ConvTasNet.backward: the workspace of this forward was overwritten by a later forward of the same "
-                             "shape (or evicted); run backward before the next forward of that shape")
-        # (autograd runs this in its device thread: without a scope of its own every library call of the backward pass looks
-        #  torch's current stream up again -- ~60 look-ups of ~7 us per step: round 5, tools/host_profile2.py)
-        from .._lib import stream_scope
-        with stream_scope():
-            ctx.model._run_backward(ctx.ws, grad_out)
-        return None, None, None
-
-
 class ConvTasNet(FlatModule):
+    plan_name = "ConvTasNet"
+
     def __init__(self, sources, N=128, L=40, B=128, H=256, P=3, X=7, R=2, audio_channels=2, norm_type="gLN", causal=False,
                  mask_nonlinear="relu", sample_rate=44100, segment_length=44100 * 2 * 4, skip=False, *args, **kwargs):
         super().__init__()
-        from .. import plan_tasnet
+        from .. import plan_tasnet          # (the argument P shadows the module's alias in here)
         self.cfg = cfg = plan_tasnet.TasNetConfig(sources, N=N, L=L, B=B, H=H, P=P, X=X, R=R, audio_channels=audio_channels,
                                                   norm_type=norm_type, causal=causal, mask_nonlinear=mask_nonlinear, skip=skip)
         skey = (cfg.key(), bool(os.environ.get("SEHIP_CTN_KEEP_GRADS")))      # (the test switch changes the buffer names of the plan)
-        if skey not in _STATIC_CACHE:
-            _STATIC_CACHE[skey] = plan_tasnet.TasNetStatic(cfg)
-        self.static = _STATIC_CACHE[skey]
+        self.static = self._static(skey, lambda: plan_tasnet.TasNetStatic(cfg))
         self.sources, self.C = sources, cfg.C
         self.N, self.L, self.B, self.H, self.P, self.X, self.R = N, L, B, H, P, X, R
         self.audio_channels, self.sample_rate, self.segment_length = audio_channels, sample_rate, segment_length
-        self._tables = None
-        self._ws_cap = max(1, int(os.environ.get("SEHIP_WS_CACHE", "4")))
         self._build_flat()
         self.reset_parameters()
 
@@ -91,10 +65,10 @@ class ConvTasNet(FlatModule):
         return self
 
     def workspace(self, batch, nsample):
-        dev = self._require_gpu("ConvTasNet")
+        dev = self._require_gpu()
         if self._tables is None:
             self._tables = P.TasNetDeviceTables(self.static, dev)
-        return self._lru_get((batch, nsample), self._ws_cap, lambda: P.TasNetWorkspace(self.static, self._tables, batch, nsample, dev))
+        return self._lru_get((batch, nsample), lambda: P.TasNetWorkspace(self.static, self._tables, batch, nsample, dev))
 
     def _run_forward(self, wav):
         ws = self.workspace(wav.shape[0], wav.shape[-1])
@@ -111,10 +85,4 @@ class ConvTasNet(FlatModule):
     def forward(self, mixture):
         if mixture.dim() != 3 or mixture.shape[1] != self.audio_channels:
             raise SehipError(f"ConvTasNet.forward: [M, {self.audio_channels}, T] expected, got {tuple(mixture.shape)}")
-        if not mixture.is_cuda:
-            raise SehipError("ConvTasNet.forward got a CPU tensor: the HIP path needs a gfx950 GPU (no CPU fallback)")
-        if torch.is_grad_enabled():
-            if self._anchor is None or self._anchor.device != mixture.device:
-                self._anchor = torch.zeros(1, device=mixture.device, requires_grad=True)
-            return _TasNetFunction.apply(self, mixture, self._anchor)
-        return self._run_forward(mixture).out.clone()
+        return self._run_plan(mixture, torch.is_grad_enabled())

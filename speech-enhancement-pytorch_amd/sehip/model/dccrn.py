@@ -16,43 +16,9 @@ from .. import plan, ops
 from .._lib import SehipError
 from .flat import FlatModule, _Node
 
-_STATIC_CACHE = {}
-
-
-def _static_for(cfg, deterministic=False):
-    # (the experiment switches that DCCRNStatic reads when it is built are part of the key)
-    switches = tuple(os.environ.get(k) for k in ("SEHIP_NO_FUSE_STATS", "SEHIP_NO_FUSE_STATS64", "SEHIP_NO_FUSE_STATS32", "SEHIP_DEC_SPLIT"))
-    key = (tuple(cfg.kernel_num), cfg.rnn_layers, cfg.rnn_units, cfg.win_len, cfg.win_inc, cfg.fft_len, cfg.length, cfg.masking_mode, str(cfg.win_type), bool(cfg.use_cbn), bool(cfg.use_clstm), switches,
-           bool(deterministic))
-    if key not in _STATIC_CACHE:
-        _STATIC_CACHE[key] = plan.DCCRNStatic(cfg, deterministic=deterministic)
-    return _STATIC_CACHE[key]
-
-
-class _DCCRNFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, model, wav, anchor):
-        ctx.model = model
-        ctx.ws = model._run_forward(wav)
-        ctx.generation = ctx.ws.generation
-        return ctx.ws.wav.view(wav.shape[0], 1, -1).clone()
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        # the activations live in the workspace shared by every call of this (batch, samples) shape, not in autograd's
-        # saved tensors: a second forward of the same shape before this backward has overwritten them
-        if ctx.generation != ctx.ws.generation or ctx.ws.closed:
-            raise SehipError("DCCRN.backward: the workspace of this forward was overwritten by a later forward of the same "
-                             "shape (or evicted); run backward before the next forward of that shape")
-        # (autograd runs this in its device thread: without a scope of its own every library call of the backward pass looks
-        #  torch's current stream up again -- ~60 look-ups of ~7 us per step: round 5, tools/host_profile2.py)
-        from .._lib import stream_scope
-        with stream_scope():
-            ctx.model._run_backward(ctx.ws, grad_out)
-        return None, None, None
-
-
 class DCCRN(FlatModule):
+    plan_name = "DCCRN"
+
     def __init__(self, rnn_layers=2, rnn_units=128, win_len=400, win_inc=100, fft_len=512, length=16384, win_type="hann",
                  masking_mode="E", use_clstm=True, use_cbn=True, kernel_size=5, kernel_num=[16, 32, 64, 128, 256, 256],
                  *args, **kwargs):
@@ -63,9 +29,7 @@ class DCCRN(FlatModule):
                                           kernel_num=list(kernel_num))
         self.win_len, self.win_inc, self.fft_len, self.rnn_units = win_len, win_inc, fft_len, rnn_units
         self.masking_mode, self.kernel_num = masking_mode, cfg.kernel_num
-        self.static = _static_for(cfg)
-        self._tables = None
-        self._ws_cap = max(1, int(os.environ.get("SEHIP_WS_CACHE", "4")))
+        self.static = self._static_for(cfg)
         self.grad_range_hook = None   # data-parallel: called with (lo, hi, stream) when flat_grads[lo:hi] is final (see plan.backward)
 
         # persistent STFT buffers (checkpoint compatibility; the FFT kernels do not read them)
@@ -79,6 +43,13 @@ class DCCRN(FlatModule):
         self._build_flat(list_roots=("encoder", "decoder"))   # registration order encoder, decoder, enhance = the reference's
                                                                # parameters() order (optimizer state indices interchange)
         self.reset_parameters()
+
+    def _static_for(self, cfg, deterministic=False):
+        # (the experiment switches that DCCRNStatic reads when it is built are part of the key)
+        switches = tuple(os.environ.get(k) for k in ("SEHIP_NO_FUSE_STATS", "SEHIP_NO_FUSE_STATS64", "SEHIP_NO_FUSE_STATS32", "SEHIP_DEC_SPLIT"))
+        key = (tuple(cfg.kernel_num), cfg.rnn_layers, cfg.rnn_units, cfg.win_len, cfg.win_inc, cfg.fft_len, cfg.length, cfg.masking_mode, str(cfg.win_type), bool(cfg.use_cbn), bool(cfg.use_clstm), switches,
+               bool(deterministic))
+        return self._static(key, lambda: plan.DCCRNStatic(cfg, deterministic=deterministic))
 
     def reset_parameters(self):
         """Same distributions as the reference constructors: conv N(0,0.05)/bias 0 (src/model/dccrn.py:352-355,
@@ -110,11 +81,10 @@ class DCCRN(FlatModule):
 
     # ---- HIP path -------------------------------------------------------------------------------------
     def workspace(self, batch, nsample):
-        dev = self._require_gpu("DCCRN")
+        dev = self._require_gpu()
         if self._tables is None:
             self._tables = plan.DeviceTables(self.static, dev)
-        return self._lru_get((batch, nsample), self._ws_cap,
-                             lambda: plan.DCCRNWorkspace(self.static, self._tables, batch, nsample, dev))
+        return self._lru_get((batch, nsample), lambda: plan.DCCRNWorkspace(self.static, self._tables, batch, nsample, dev))
 
     def set_deterministic(self, on=True):
         """The reference's `solver.cudnn_deterministic` switch (src/conf/config.yaml:130, src/utils.py:108-111) for this model: the plan
@@ -125,7 +95,7 @@ class DCCRN(FlatModule):
         on = bool(on)
         if on == self.static.deterministic:
             return self
-        self.static = _static_for(self.cfg, deterministic=on)
+        self.static = self._static_for(self.cfg, deterministic=on)
         self._tables = None
         for ws in list(self._ws.values()):
             ws.close()
@@ -163,30 +133,22 @@ class DCCRN(FlatModule):
         ws.forward(x, self._flat, self._bflat, self._nbt, training=self.training)
         return ws
 
+    def _output(self, ws, x):
+        return ws.wav.view(x.shape[0], 1, -1).clone()
+
     def _run_backward(self, ws, grad_out):
         if not self.training:
             raise SehipError("DCCRN.backward in eval mode (running-statistics BatchNorm) is not built")
         g = grad_out.reshape(ws.B, ws.length).contiguous().float()
-        accumulating = self._grads_live and self._params[0][1].grad is not None
-        hook = self.grad_range_hook if not accumulating else None   # not when accumulating
-        tail = self._tail_sink if (hook is None and not accumulating) else None      # FlatOptimizer's accumulators (single replica)
+        hook = self.grad_range_hook if not (self._grads_live and self._params[0][1].grad is not None) else None   # not when accumulating
+        tail = self._tail_for_backward()              # FlatOptimizer's accumulators (single replica, not accumulating)
         self._backward_into_flat(lambda dst: ws.backward(g, self._flat, dst, range_ready=hook, tail=tail))
-        if tail is not None:
-            self._tail_done = self._tail_counted = self._tail_dirty = True
-        else:
-            self._tail_done = False          # (an accumulating or data-parallel pass: the optimizer takes its sums from the final buffer)
+        self._tail_mark(tail)
 
     def forward(self, inputs, lens=None):
         if inputs.dim() == 2:
             inputs = inputs.unsqueeze(1)
-        if not inputs.is_cuda:
-            raise SehipError("DCCRN.forward got a CPU tensor: the HIP path needs a gfx950 GPU (no CPU fallback)")
-        if torch.is_grad_enabled() and self.training:
-            if self._anchor is None or self._anchor.device != inputs.device:
-                self._anchor = torch.zeros(1, device=inputs.device, requires_grad=True)
-            return _DCCRNFunction.apply(self, inputs, self._anchor)
-        ws = self._run_forward(inputs)
-        return ws.wav.view(inputs.shape[0], 1, -1).clone()
+        return self._run_plan(inputs, torch.is_grad_enabled() and self.training)
 
     def get_params(self, weight_decay=0.0):
         """Same grouping helper as the reference (src/model/dccrn.py:231-246)."""

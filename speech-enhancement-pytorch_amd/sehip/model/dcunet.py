@@ -9,7 +9,6 @@ Built: the complex network (data_type=True), model_depth 10 and 20, zero padding
 channels (model_complexity <= 90: 63 / 126 channels, the paper's "Large" network).
 """
 import math
-import os
 
 import torch
 from torch import nn
@@ -18,43 +17,18 @@ from .. import plan_dcunet as P
 from .._lib import SehipError
 from .flat import FlatModule
 
-_STATIC_CACHE = {}
-
-
-class _DCUNetFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, model, spec, anchor):
-        ctx.model = model
-        ctx.ws = model._run_forward(spec)
-        ctx.generation = ctx.ws.generation
-        return ctx.ws.out.clone()
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        if ctx.generation != ctx.ws.generation or ctx.ws.closed:
-            raise SehipError("DCUnet.backward: the workspace of this forward was overwritten by a later forward of the same shape "
-                             "(or evicted); run backward before the next forward of that shape")
-        # (autograd runs this in its device thread: without a scope of its own every library call of the backward pass looks
-        #  torch's current stream up again -- ~60 look-ups of ~7 us per step: round 5, tools/host_profile2.py)
-        from .._lib import stream_scope
-        with stream_scope():
-            ctx.model._run_backward(ctx.ws, grad_out)
-        return None, None, None
-
-
 class DCUnet(FlatModule):
+    plan_name = "DCUnet"
+
     def __init__(self, audio_channels=1, data_type=False, model_complexity=45, model_depth=20, padding_mode="zeros",
                  masking_mode="E", *args, **kwargs):
         super().__init__()
         self.cfg = cfg = P.DCUNetConfig(audio_channels=audio_channels, data_type=data_type, model_complexity=model_complexity,
                                         model_depth=model_depth, padding_mode=padding_mode, masking_mode=masking_mode)
-        if cfg.key() not in _STATIC_CACHE:
-            _STATIC_CACHE[cfg.key()] = P.DCUNetStatic(cfg)
-        self.static = _STATIC_CACHE[cfg.key()]
+        self.static = self._static(cfg.key(), lambda: P.DCUNetStatic(cfg))
         self.data_type, self.padding_mode, self.masking_mode = data_type, padding_mode, masking_mode
         self.model_length = model_depth // 2
         self._plans, self._tables_by_plan = {}, {}
-        self._ws_cap = max(1, int(os.environ.get("SEHIP_WS_CACHE", "4")))
         self._build_flat()
         # the reference registers every block twice: add_module("encoder{i}") and the ModuleLists assigned at the end
         self.decoders = nn.ModuleList([getattr(self, f"decoder{i}") for i in range(self.model_length)])
@@ -93,13 +67,13 @@ class DCUnet(FlatModule):
         return self
 
     def workspace(self, batch, n_bins, n_frames):
-        dev = self._require_gpu("DCUnet")
+        dev = self._require_gpu()
         gk = (n_bins, n_frames)
         if gk not in self._plans:
             self._plans[gk] = P.DCUNetPlan(self.static, n_bins, n_frames)
         if gk not in self._tables_by_plan:
             self._tables_by_plan[gk] = P.DCUNetDeviceTables(self._plans[gk], dev)
-        return self._lru_get((batch, n_bins, n_frames), self._ws_cap,
+        return self._lru_get((batch, n_bins, n_frames),
                              lambda: P.DCUNetWorkspace(self._plans[gk], self._tables_by_plan[gk], batch, dev))
 
     def _run_forward(self, spec):
@@ -120,10 +94,4 @@ class DCUnet(FlatModule):
     def forward(self, x):
         if x.dim() != 5 or x.shape[-1] != 2 or x.shape[1] != 1:
             raise SehipError(f"DCUnet.forward: [B, 1, F, T, 2] expected (stft_custom's layout), got {tuple(x.shape)}")
-        if not x.is_cuda:
-            raise SehipError("DCUnet.forward got a CPU tensor: the HIP path needs a gfx950 GPU (no CPU fallback)")
-        if torch.is_grad_enabled() and self.training:
-            if self._anchor is None or self._anchor.device != x.device:
-                self._anchor = torch.zeros(1, device=x.device, requires_grad=True)
-            return _DCUNetFunction.apply(self, x, self._anchor)
-        return self._run_forward(x).out.clone()
+        return self._run_plan(x, torch.is_grad_enabled() and self.training)

@@ -7,7 +7,6 @@ into one flat fp32 buffer; forward / backward run the HIP kernels through the C 
 Built: the structure of the constructor defaults (sehip/plan_demucs.py lists the options and limits).
 """
 import math
-import os
 
 import torch
 
@@ -15,31 +14,10 @@ from .. import plan_demucs as P
 from .._lib import SehipError
 from .flat import FlatModule
 
-_STATIC_CACHE = {}
-
-
-class _DemucsFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, model, mix, anchor):
-        ctx.model = model
-        ctx.ws = model._run_forward(mix, need_backward=True)      # (grad mode is off inside Function.forward: say it explicitly)
-        ctx.generation = ctx.ws.generation
-        return ctx.ws.out.clone()
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        if ctx.generation != ctx.ws.generation or ctx.ws.closed:
-            raise SehipError("Demucs.backward: the workspace of this forward was overwritten by a later forward of the same shape "
-                             "(or evicted); run backward before the next forward of that shape")
-        # (autograd runs this in its device thread: without a scope of its own every library call of the backward pass looks
-        #  torch's current stream up again -- ~60 look-ups of ~7 us per step: round 5, tools/host_profile2.py)
-        from .._lib import stream_scope
-        with stream_scope():
-            ctx.model._run_backward(ctx.ws, grad_out)
-        return None, None, None
-
-
 class Demucs(FlatModule):
+    plan_name = "Demucs"
+    ws_cache_default = 2
+
     def __init__(self, sources, audio_channels=2, channels=64, growth=2., depth=6, rewrite=True, lstm_layers=0, kernel_size=8, stride=4,
                  context=1, gelu=True, glu=True, norm_starts=4, norm_groups=4, dconv_mode=1, dconv_depth=2, dconv_comp=4, dconv_attn=4,
                  dconv_lstm=4, dconv_init=1e-4, normalize=True, resample=True, rescale=0.1, samplerate=44100, segment=4 * 10, *args, **kwargs):
@@ -49,14 +27,10 @@ class Demucs(FlatModule):
                                         norm_starts=norm_starts, norm_groups=norm_groups, dconv_mode=dconv_mode, dconv_depth=dconv_depth,
                                         dconv_comp=dconv_comp, dconv_attn=dconv_attn, dconv_lstm=dconv_lstm, dconv_init=dconv_init,
                                         normalize=normalize, resample=resample, rescale=rescale)
-        if cfg.key() not in _STATIC_CACHE:
-            _STATIC_CACHE[cfg.key()] = P.DemucsStatic(cfg)
-        self.static = _STATIC_CACHE[cfg.key()]
+        self.static = self._static(cfg.key(), lambda: P.DemucsStatic(cfg))
         self.audio_channels, self.sources, self.kernel_size, self.context, self.stride, self.depth = audio_channels, sources, kernel_size, context, stride, depth
         self.resample, self.channels, self.normalize, self.samplerate, self.segment = resample, channels, normalize, samplerate, segment
-        self._tables = None
         self.grad_range_hook = None   # data-parallel: called with (lo, hi, stream) when flat_grads[lo:hi] is final (plan_demucs.backward)
-        self._ws_cap = max(1, int(os.environ.get("SEHIP_WS_CACHE", "2")))
         self._build_flat(list_roots=("encoder", "decoder"))
         self.reset_parameters()
 
@@ -123,10 +97,10 @@ class Demucs(FlatModule):
         return super().load_state_dict(state, strict=strict, **kw)
 
     def workspace(self, batch, nsample):
-        dev = self._require_gpu("Demucs")
+        dev = self._require_gpu()
         if self._tables is None:
             self._tables = P.DemucsDeviceTables(self.static, dev)
-        return self._lru_get((batch, nsample), self._ws_cap, lambda: P.DemucsWorkspace(self.static, self._tables, batch, nsample, dev))
+        return self._lru_get((batch, nsample), lambda: P.DemucsWorkspace(self.static, self._tables, batch, nsample, dev))
 
     def step_guard(self):
         """Device word the fused optimizer checks (sehip_opt_step_g): the sticky hand-off time-out word of the workspace the last
@@ -145,7 +119,7 @@ class Demucs(FlatModule):
         self._note_graph_epoch(ws)
         return lost
 
-    def _run_forward(self, mix, need_backward):
+    def _run_forward(self, mix, need_backward=True):      # (_PlanFunction: grad mode is off inside Function.forward, so True is the default)
         ws = self.workspace(mix.shape[0], mix.shape[-1])
         self._last_ws = ws
         ws.generation += 1
@@ -163,10 +137,4 @@ class Demucs(FlatModule):
     def forward(self, mix):
         if mix.dim() != 3 or mix.shape[1] != self.audio_channels:
             raise SehipError(f"Demucs.forward: [B, {self.audio_channels}, T] expected, got {tuple(mix.shape)}")
-        if not mix.is_cuda:
-            raise SehipError("Demucs.forward got a CPU tensor: the HIP path needs a gfx950 GPU (no CPU fallback)")
-        if torch.is_grad_enabled():
-            if self._anchor is None or self._anchor.device != mix.device:
-                self._anchor = torch.zeros(1, device=mix.device, requires_grad=True)
-            return _DemucsFunction.apply(self, mix, self._anchor)
-        return self._run_forward(mix, need_backward=False).out.clone()
+        return self._run_plan(mix, torch.is_grad_enabled(), need_backward=False)

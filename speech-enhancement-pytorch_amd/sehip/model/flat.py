@@ -5,13 +5,16 @@ Why flat: the data-parallel exchange is a single RCCL all-reduce of `flat_grads`
 (`flat_params`, `flat_grads`, m, v) (sehip/optim.py), and the table-driven weight packing of the GEMM engine indexes
 `flat_params` directly.  A subclass provides `self.static.layout` (sehip.plan.ParamLayout) before calling `_build_flat()`.
 """
+import os
 from collections import OrderedDict
 
 import numpy as np
 import torch
 from torch import nn
 
-from .._lib import SehipError
+from .._lib import SehipError, stream_scope
+
+_STATIC_CACHE = {}      # (model class, configuration key) -> the plan's static part, shared by every model of that configuration
 
 
 class _Node(nn.Module):
@@ -28,16 +31,64 @@ def _clone_state_hook(module, state_dict, prefix, local_metadata):
     return state_dict
 
 
+class _PlanFunction(torch.autograd.Function):
+    """The train step's forward / backward of every model: the activations live in the workspace shared by every call of one input
+    shape, not in autograd's saved tensors."""
+
+    @staticmethod
+    def forward(ctx, model, x, anchor):
+        ctx.model = model
+        ctx.ws = model._run_forward(x)
+        ctx.generation = ctx.ws.generation
+        return model._output(ctx.ws, x)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        # a second forward of the same shape before this backward has overwritten the activations
+        if ctx.generation != ctx.ws.generation or ctx.ws.closed:
+            raise SehipError(f"{ctx.model.plan_name}.backward: the workspace of this forward was overwritten by a later forward of the same "
+                             "shape (or evicted); run backward before the next forward of that shape")
+        # (autograd runs this in its device thread: without a scope of its own every library call of the backward pass looks
+        #  torch's current stream up again -- ~60 look-ups of ~7 us per step: round 5, tools/host_profile2.py)
+        with stream_scope():
+            ctx.model._run_backward(ctx.ws, grad_out)
+        return None, None, None
+
+
+class _EvalGuard(torch.autograd.Function):
+    """Identity whose backward raises: an eval-mode output takes part in a graph (losses are computed on it) but has no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, name):
+        ctx.name = name
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        raise SehipError(f"{ctx.name}.backward in eval mode: the backward pass is built for batch statistics only (call model.train())")
+
+
 class FlatModule(nn.Module):
+    plan_name = None        # the model's name in the messages of the HIP path
+    ws_cache_default = 4    # workspaces (input shapes) kept per model unless SEHIP_WS_CACHE says otherwise
+
+    def _static(self, key, make):
+        """The plan's static part for this configuration, built once per process."""
+        key = (type(self), key)
+        if key not in _STATIC_CACHE:
+            _STATIC_CACHE[key] = make()
+        return _STATIC_CACHE[key]
+
     def _build_flat(self, list_roots=()):
         """Creates the flat storage and registers every tensor of `self.static.layout.specs` under its dotted name.
         `list_roots`: top-level names that are nn.ModuleList in the reference (integer children)."""
         L = self.static.layout
         self._flat = torch.zeros(L.n_params)
-        self._gflat = None
+        self._gflat = self._tables = None
         self._bflat = torch.zeros(max(L.n_buffers, 1))
         self._nbt = torch.zeros(len(L.nbt_names), dtype=torch.int64)
         self._ws = OrderedDict()
+        self._ws_cap = max(1, int(os.environ.get("SEHIP_WS_CACHE", self.ws_cache_default)))
         self.storage_epoch = 0        # bumped whenever the flat buffers are re-created (captured hipGraphs go stale)
         self._anchor = None
         self._grads_live = False
@@ -140,18 +191,40 @@ class FlatModule(nn.Module):
             off, shape = L.param_off[name]
             p.grad = g[off:off + p.numel()].view(shape)
 
-    def _require_gpu(self, what):
+    def _require_gpu(self):
         dev = self._flat.device
         if dev.type != "cuda":
-            raise SehipError(f"{what} parameters are on {dev}: the HIP path needs a gfx950 GPU (no CPU fallback); "
+            raise SehipError(f"{self.plan_name} parameters are on {dev}: the HIP path needs a gfx950 GPU (no CPU fallback); "
                              "call model.to('cuda') first")
         return dev
 
-    def _lru_get(self, key, cap, make):
+    def _grad_anchor(self, device):
+        """What makes autograd call _PlanFunction.backward: the parameters themselves are not its inputs."""
+        if self._anchor is None or self._anchor.device != device:
+            self._anchor = torch.zeros(1, device=device, requires_grad=True)
+        return self._anchor
+
+    def _output(self, ws, x):
+        return ws.out.clone()
+
+    def _run_plan(self, x, train_step, **forward_only):
+        """forward() behind the model's own shape check.  train_step: through _PlanFunction, so that backward() runs the plan's
+        backward pass; else forward only, _run_forward taking `forward_only` as well."""
+        if not x.is_cuda:
+            raise SehipError(f"{self.plan_name}.forward got a CPU tensor: the HIP path needs a gfx950 GPU (no CPU fallback)")
+        if train_step:
+            return _PlanFunction.apply(self, x, self._grad_anchor(x.device))
+        return self._output(self._run_forward(x, **forward_only), x)
+
+    def _eval_guarded(self, out):
+        """an eval-mode output under grad mode: forward only, a backward pass through the running statistics is not built"""
+        return _EvalGuard.apply(out.requires_grad_(True), self.plan_name)
+
+    def _lru_get(self, key, make):
         """Workspace cache: least recently used shapes are evicted first (never one a captured hipGraph points into)."""
         ws = self._ws.get(key)
         if ws is None:
-            while len(self._ws) >= cap:
+            while len(self._ws) >= self._ws_cap:
                 victim = next((k for k, w in self._ws.items() if not w.pinned), None)
                 if victim is None:
                     break

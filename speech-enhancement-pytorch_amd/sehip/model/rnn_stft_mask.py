@@ -11,7 +11,6 @@ As in the reference the features are |re^2 - im^2| and the recurrence runs along
 64-bit seed from torch's default CPU generator at construction, a step counter lives on the device and is advanced there.
 """
 import math
-import os
 
 import torch
 
@@ -19,54 +18,17 @@ from .. import plan_rnnmask as P
 from .._lib import SehipError
 from .flat import FlatModule
 
-_STATIC_CACHE = {}
-
-
-class _RnnMaskFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, model, x, anchor):
-        ctx.model = model
-        ctx.ws = model._run_forward(x)
-        ctx.generation = ctx.ws.generation
-        return ctx.ws.out.clone()
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        if ctx.generation != ctx.ws.generation or ctx.ws.closed:
-            raise SehipError("RNNBaseSTFTMask.backward: the workspace of this forward was overwritten by a later forward of the same "
-                             "shape (or evicted); run backward before the next forward of that shape")
-        from .._lib import stream_scope
-        with stream_scope():
-            ctx.model._run_backward(ctx.ws, grad_out)
-        return None, None, None
-
-
-class _EvalGuard(torch.autograd.Function):
-    """Identity whose backward raises: an eval-mode output takes part in a graph (losses are computed on it) but has no gradient."""
-
-    @staticmethod
-    def forward(ctx, x):
-        return x.view_as(x)
-
-    @staticmethod
-    def backward(ctx, g):
-        raise SehipError("RNNBaseSTFTMask.backward in eval mode: the backward pass is built for batch statistics only (call model.train())")
-
-
 class RNNBaseSTFTMask(FlatModule):
+    plan_name = "RNNBaseSTFTMask"
+
     def __init__(self, num_spk=2, audio_channels=2, n_fft=512, hop_length=256, sample_rate=16000, rnn_hidden=256, rnn_layer=2,
                  rnn_type="rnn", drop_out=0.5, activation="relu", bidirectional=False, *args, **kwarg):
         super().__init__()
         self.cfg = cfg = P.RnnMaskConfig(num_spk=num_spk, audio_channels=audio_channels, n_fft=n_fft, hop_length=hop_length,
                                          sample_rate=sample_rate, rnn_hidden=rnn_hidden, rnn_layer=rnn_layer, rnn_type=rnn_type,
                                          drop_out=drop_out, activation=activation, bidirectional=bidirectional)
-        skey = cfg.key()
-        if skey not in _STATIC_CACHE:
-            _STATIC_CACHE[skey] = P.RnnMaskStatic(cfg)
-        self.static = _STATIC_CACHE[skey]
+        self.static = self._static(cfg.key(), lambda: P.RnnMaskStatic(cfg))
         self.audio_channels, self.num_spk, self.n_fft, self.hop_length, self.sample_rate = audio_channels, num_spk, n_fft, hop_length, sample_rate
-        self._tables = None
-        self._ws_cap = max(1, int(os.environ.get("SEHIP_WS_CACHE", "4")))
         self._ws_guard = 0           # tests: canary bands around every buffer of workspaces created from here on
         self._build_flat()
         # gradients land in the flat buffer in the parameters' own layout: there is no un-pack launch that could take the optimizer's clip /
@@ -106,8 +68,8 @@ class RNNBaseSTFTMask(FlatModule):
         return self._drop_counter
 
     def workspace(self, batch, nframe):
-        dev = self._require_gpu("RNNBaseSTFTMask")
-        return self._lru_get((batch, self.cfg.audio_channels, nframe), self._ws_cap,
+        dev = self._require_gpu()
+        return self._lru_get((batch, self.cfg.audio_channels, nframe),
                              lambda: P.RnnMaskWorkspace(self.static, batch, nframe, dev, guard=self._ws_guard))
 
     def _run_forward(self, x):
@@ -124,13 +86,5 @@ class RNNBaseSTFTMask(FlatModule):
         cfg = self.cfg
         if inputs.dim() != 5 or inputs.shape[1] != cfg.audio_channels or inputs.shape[2] != cfg.F or inputs.shape[4] != 2:
             raise SehipError(f"RNNBaseSTFTMask.forward: [B, {cfg.audio_channels}, {cfg.F}, T, 2] expected, got {tuple(inputs.shape)}")
-        if not inputs.is_cuda:
-            raise SehipError("RNNBaseSTFTMask.forward got a CPU tensor: the HIP path needs a gfx950 GPU (no CPU fallback)")
-        if torch.is_grad_enabled():
-            if not self.training:
-                ws = self._run_forward(inputs)
-                return _EvalGuard.apply(ws.out.clone().requires_grad_(True))
-            if self._anchor is None or self._anchor.device != inputs.device:
-                self._anchor = torch.zeros(1, device=inputs.device, requires_grad=True)
-            return _RnnMaskFunction.apply(self, inputs, self._anchor)
-        return self._run_forward(inputs).out.clone()
+        out = self._run_plan(inputs, torch.is_grad_enabled() and self.training)
+        return self._eval_guarded(out) if torch.is_grad_enabled() and not self.training else out

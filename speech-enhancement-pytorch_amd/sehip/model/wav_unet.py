@@ -8,7 +8,6 @@ samples with at least two frames in the middle block (the reference fails in tor
 statistics and updates the running ones as nn.BatchNorm1d does; eval uses the running statistics (forward only).
 """
 import math
-import os
 
 import torch
 
@@ -16,39 +15,14 @@ from .. import plan_wavunet as P
 from .._lib import SehipError
 from .flat import FlatModule
 
-_STATIC_CACHE = {}
-
-
-class _WavUnetFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, model, wav, anchor):
-        ctx.model = model
-        ctx.ws = model._run_forward(wav)
-        ctx.generation = ctx.ws.generation
-        return ctx.ws.out.clone()
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        if ctx.generation != ctx.ws.generation or ctx.ws.closed:
-            raise SehipError("WavUnet.backward: the workspace of this forward was overwritten by a later forward of the same "
-                             "shape (or evicted); run backward before the next forward of that shape")
-        from .._lib import stream_scope
-        with stream_scope():
-            ctx.model._run_backward(ctx.ws, grad_out)
-        return None, None, None
-
-
 class WavUnet(FlatModule):
+    plan_name = "WavUnet"
+
     def __init__(self, unet_nlayers=12, channels_interval=24, *args, **kwargs):
         super().__init__()
         self.cfg = cfg = P.WavUnetConfig(unet_nlayers=unet_nlayers, channels_interval=channels_interval)
-        skey = cfg.key()
-        if skey not in _STATIC_CACHE:
-            _STATIC_CACHE[skey] = P.WavUnetStatic(cfg)
-        self.static = _STATIC_CACHE[skey]
+        self.static = self._static(cfg.key(), lambda: P.WavUnetStatic(cfg))
         self.n_layers, self.channels_interval = unet_nlayers, channels_interval
-        self._tables = None
-        self._ws_cap = max(1, int(os.environ.get("SEHIP_WS_CACHE", "4")))
         self._build_flat(list_roots=("encoder", "decoder"))
         mods = dict(self._modules)             # the reference registers encoder, middle, decoder, out: state_dict() follows that order
         self._modules.clear()
@@ -78,10 +52,10 @@ class WavUnet(FlatModule):
         return P.valid_lengths(length, self.cfg.n)[1]
 
     def workspace(self, batch, nsample):
-        dev = self._require_gpu("WavUnet")
+        dev = self._require_gpu()
         if self._tables is None:
             self._tables = P.WavUnetDeviceTables(self.static, dev)
-        return self._lru_get((batch, nsample), self._ws_cap, lambda: P.WavUnetWorkspace(self.static, self._tables, batch, nsample, dev))
+        return self._lru_get((batch, nsample), lambda: P.WavUnetWorkspace(self.static, self._tables, batch, nsample, dev))
 
     def _run_forward(self, wav):
         ws = self.workspace(wav.shape[0], wav.shape[-1])
@@ -98,27 +72,6 @@ class WavUnet(FlatModule):
     def forward(self, input):
         if input.dim() != 3 or input.shape[1] != 1:
             raise SehipError(f"WavUnet.forward: [B, 1, T] expected, got {tuple(input.shape)}")
-        if not input.is_cuda:
-            raise SehipError("WavUnet.forward got a CPU tensor: the HIP path needs a gfx950 GPU (no CPU fallback)")
-        if torch.is_grad_enabled():
-            if not self.training:
-                # forward only: a backward pass through the running statistics is not built (as for DCCRN and DCUnet)
-                ws = self._run_forward(input)
-                out = ws.out.clone().requires_grad_(True)
-                return _EvalGuard.apply(out)
-            if self._anchor is None or self._anchor.device != input.device:
-                self._anchor = torch.zeros(1, device=input.device, requires_grad=True)
-            return _WavUnetFunction.apply(self, input, self._anchor)
-        return self._run_forward(input).out.clone()
+        out = self._run_plan(input, torch.is_grad_enabled() and self.training)
+        return self._eval_guarded(out) if torch.is_grad_enabled() and not self.training else out
 
-
-class _EvalGuard(torch.autograd.Function):
-    """Identity whose backward raises: an eval-mode output takes part in a graph (losses are computed on it) but has no gradient."""
-
-    @staticmethod
-    def forward(ctx, x):
-        return x.view_as(x)
-
-    @staticmethod
-    def backward(ctx, g):
-        raise SehipError("WavUnet.backward in eval mode: the backward pass is built for batch statistics only (call model.train())")

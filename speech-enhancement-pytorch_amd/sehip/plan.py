@@ -21,6 +21,7 @@ import torch
 from . import _lib
 from ._lib import call, ptr, stream, SehipError
 from . import ops
+from .workspace import Buf, GemmWorkspace, gather_ordered_device_tables, gather_ordered_unpack_table      # (Buf, gather_ordered_unpack_table: importable from here as before)
 
 BF16 = torch.bfloat16
 
@@ -854,34 +855,9 @@ class DCCRNStatic:
         return tab
 
 
-def gather_ordered_unpack_table(tab, tensor_offsets):
-    """The un-pack table [n_params][4] with the rows of every tensor sorted by the address of their first packed entry, and the
-    parameter each row un-packs (int32 [n_params]): the form sehip_unpack_grad_sums_perm takes.  A convolution weight
-    [co][ci][kf][kt] reads dW[n][(kt, kf, ci)]: in parameter order neighbouring lanes gather floats 5 C apart (one 64-byte sector per
-    4-byte read), in gather order they read a run of `ci`.  Rows never leave their tensor: the per-tensor sums are taken by position."""
-    tab = np.asarray(tab)
-    n = tab.shape[0]
-    first = tab[:, 0].astype(np.int64) >> 1
-    first[tab[:, 0] < 0] = np.iinfo(np.int64).max >> 2          # parameters without a packed entry stay where they are, at the end
-    offs = np.asarray(tensor_offsets, dtype=np.int64)
-    tensor_of = np.searchsorted(offs, np.arange(n, dtype=np.int64), side="right") - 1
-    perm = np.lexsort((np.arange(n), first, tensor_of)).astype(np.int32)     # by tensor, then by gather address, stable
-    assert np.array_equal(tensor_of[perm], tensor_of)
-    return np.ascontiguousarray(tab[perm]), perm
-
-
 # --------------------------------------------------------------------------------------------------
 # dynamic part: buffers for one (batch, length), bound descriptors, launch sequences
 # --------------------------------------------------------------------------------------------------
-class Buf:
-    def __init__(self, t, tst, f, c, t0):
-        self.t, self.Tst, self.F, self.C, self.t0 = t, tst, f, c, t0
-
-    @property
-    def ptr(self):
-        return self.t.data_ptr()
-
-
 class DeviceTables:
     """Device copies of the static tables (shared by every workspace of a model on one device)."""
 
@@ -890,23 +866,22 @@ class DeviceTables:
         self.wtab, self.btab, self.utab = f(st.wtab), f(st.btab), f(st.utab)
         self.ktab, self.ntab = f(st.ktab), f(st.ntab)
         self.tensor_offsets = f(st.layout.tensor_offsets)
-        self.utab_g = self.uperm = None                 # the fused tail's un-pack in gather order (SEHIP_NO_UNPACK_PERM: parameter order)
-        if not os.environ.get("SEHIP_NO_UNPACK_PERM"):
-            tg, pm = gather_ordered_unpack_table(st.utab, st.layout.tensor_offsets)
-            self.utab_g, self.uperm = f(tg), f(pm)
+        self.utab_g, self.uperm = gather_ordered_device_tables(st.utab, st.layout.tensor_offsets, f)
         cfg = st.cfg
         self.window = f(ops.window_of(cfg.win_type, cfg.win_len))
         self.wpack = torch.zeros(st.n_wpack, dtype=BF16, device=device)
         self.bpack = torch.zeros(max(st.n_bpack, 4), dtype=torch.float32, device=device)
 
 
-class DCCRNWorkspace:
+class DCCRNWorkspace(GemmWorkspace):
+    event_attrs = ("_events", "_fs_events")
+    event_pool = 32
+
     def __init__(self, st: DCCRNStatic, tables: DeviceTables, B, N, device):
+        super().__init__()
         cfg = st.cfg
         self.st, self.tb, self.B, self.N, self.device = st, tables, B, N, device
-        self.generation = 0     # bumped by every forward (a backward checks that its activations are still the live ones)
-        self.pinned = False     # a captured hipGraph holds raw pointers into this workspace: never evict
-        self.closed = False
+        self.side, self._side_handle = None, None
         self.T = T = ops.stft_frames(N, cfg.win_len, cfg.win_inc)
         if T < 1:
             raise SehipError(f"input of {N} samples is shorter than one frame")
@@ -1020,7 +995,6 @@ class DCCRNWorkspace:
         self._bn_cr = {pre: cr for pre, cr in st.bn}
         self.mode = {"E": 0, "C": 1, "R": 2}[cfg.masking_mode]
         # the weight-gradient stream.  SEHIP_SIDE_PRIORITY=1: created through the C ABI with the device's lowest priority
-        self.side, self._side_handle = None, None
         if not os.environ.get("SEHIP_NO_SIDE_STREAM"):
             if os.environ.get("SEHIP_SIDE_PRIORITY"):
                 with torch.cuda.device(device):
@@ -1031,8 +1005,6 @@ class DCCRNWorkspace:
                 self.side = torch.cuda.ExternalStream(h, device=device)
             else:
                 self.side = torch.cuda.Stream(device=device)
-        self._events, self._event_i, self._chain_dirty = [], 0, True
-        self._fs_events = []
         self.comm = None     # third stream: early un-pack + all-reduce of the decoder / LSTM gradients (data-parallel runs only)
         # The two stacked complex LSTM layers are pipelined over chunks of time steps: layer 2 (and the input product that
         # feeds it) runs chunk c on a second high-priority stream while layer 1 runs chunk c+1 (backward: the other way
@@ -1077,23 +1049,14 @@ class DCCRNWorkspace:
         self._bind()
 
     def close(self):
-        """Destroys the HIP events of this workspace (the tensors go with the Python object)."""
-        if self.closed:
-            return
-        self.closed = True
-        lib = _lib.lib()
-        for e in self._events + getattr(self, "_fs_events", []):
-            lib.sehip_event_destroy(e)
-        self._events, self._fs_events = [], []
+        super().close()
         if self._side_handle:
-            lib.sehip_stream_destroy(self._side_handle)
+            _lib.lib().sehip_stream_destroy(self._side_handle)
             self._side_handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _side_in_use(self):
+        """(also inside a stream capture: the side work is a fork / join of the graph)"""
+        return self.side is not None
 
     # ---- descriptors ---------------------------------------------------------------------------
     def _bind(self):
@@ -1244,26 +1207,11 @@ class DCCRNWorkspace:
             return "dP"
         raise KeyError(out_name)
 
-    def gemm(self, name):
-        self._chain_dirty = True
-        call("sehip_gemm", C.byref(self.desc[name]), stream())
-
     def gemm_pair(self, a, b):
         """Two products over the same sources (the two output-row parities of a transposed convolution): one launch that
         stages the input once where the library can fuse them."""
         self._chain_dirty = True
         call("sehip_gemm_pair", C.byref(self.desc[a]), C.byref(self.desc[b]), stream())
-
-    def _event(self):
-        """Round-robin pool of fence-free events (sehip_stream_depend)."""
-        if not self._events:
-            for _ in range(32):
-                e = _lib.lib().sehip_event_create()
-                if not e:
-                    raise SehipError("sehip_event_create: " + _lib.lib().sehip_last_error().decode())
-                self._events.append(e)
-        self._event_i = (self._event_i + 1) % len(self._events)
-        return self._events[self._event_i]
 
     def wgrad(self, name):
         """Weight gradients are side work (nothing in the backward chain consumes them): they go to a second HIP stream
@@ -1661,11 +1609,7 @@ class DCCRNWorkspace:
             sd = self.side.cuda_stream
             call("sehip_stream_depend", sd, stream(), self._event())
             if not self._fs_events:
-                for _ in range(6):
-                    e = _lib.lib().sehip_event_create()
-                    if not e:
-                        raise SehipError("sehip_event_create: " + _lib.lib().sehip_last_error().decode())
-                    self._fs_events.append(e)
+                self._fs_events = [self._new_event() for _ in range(6)]
             for j in split:
                 call("sehip_gemm_pair", C.byref(self.desc[f"dec{j}.fs0"]), C.byref(self.desc[f"dec{j}.fs1"]), sd)
                 call("sehip_event_record", self._fs_events[j], sd)
@@ -1754,21 +1698,12 @@ class DCCRNWorkspace:
             self.wgrad(f"enc{i}.fwd")
             if i > 0:
                 self.gemm_pair(f"enc{i}.dg0", f"enc{i}.dg1")     # one streaming launch for the outer layers (csrc/convt.hip), else the two products
-        if self.side is not None:
-            call("sehip_stream_depend", stream(), self.side.cuda_stream, self._event())
-        if tail is not None and range_ready is None:
-            # tail = (sumsq, tensor_sums, offsets, ntensors, step counter) of the fused optimizer: the un-pack also takes its sums and
-            # advances its device step counter (guarded by this workspace's hand-off word): see FlatOptimizer._arm_fused_tail
-            guard = ptr(self.l2_sync) if hasattr(self, "l2_sync") else None
-            if tb.uperm is not None:
-                call("sehip_unpack_grad_sums_perm", ptr(self.gpack), ptr(tb.utab_g), ptr(tb.uperm), n_params, ptr(grads), tail[2], tail[3],
-                     tail[0], tail[1], tail[4], guard, stream())
-            else:
-                call("sehip_unpack_grad_sums", ptr(self.gpack), ptr(tb.utab), n_params, ptr(grads), tail[2], tail[3], tail[0], tail[1], tail[4],
-                     guard, stream())
+        self.join_side()
+        if range_ready is None:
+            # (with the fused optimizer's tail the step counter is guarded by this workspace's hand-off word)
+            self.unpack(grads, tail, guard=ptr(self.l2_sync) if hasattr(self, "l2_sync") else None)
         else:
-            call("sehip_unpack_grad", ptr(self.gpack), ptr(tb.utab), lo if range_ready is not None else n_params, ptr(grads), stream())
-        if range_ready is not None:
+            call("sehip_unpack_grad", ptr(self.gpack), ptr(tb.utab), lo, ptr(grads), stream())
             range_ready(0, lo, torch.cuda.current_stream())
             call("sehip_stream_depend", stream(), self.comm.cuda_stream, self._event())
         return grads

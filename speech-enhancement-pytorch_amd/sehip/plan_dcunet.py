@@ -15,7 +15,6 @@ implicit-GEMM engine of csrc/gemm.hip (the descriptor's frame stride `tmul` cove
   weight gradients    the same descriptors with dOut as the second operand (sehip_wgrad)
 BatchNorm (two real ones) + LeakyReLU: csrc/rbn.hip.  Input transpose, 1x1 conv + tanh + mask: csrc/dcunet.hip.
 """
-import ctypes as C
 import os
 
 import numpy as np
@@ -23,6 +22,7 @@ import torch
 
 from . import _lib
 from ._lib import call, ptr, stream, SehipError
+from .workspace import Buf, GemmWorkspace, gather_ordered_device_tables
 from .plan import (Arena, CGemmDesc, GemmSpec, ParamLayout, bind_chunk_table, dense_ntab, enc_entry, npad_of, round_up, BF16)
 
 
@@ -458,35 +458,22 @@ class DCUNetPlan:
         return tab
 
 
-class Buf:
-    def __init__(self, t, T, F, Cc):
-        self.t, self.Tst, self.F, self.C = t, T, F, Cc
-
-    @property
-    def ptr(self):
-        return self.t.data_ptr()
-
-
 class DCUNetDeviceTables:
     def __init__(self, pl: DCUNetPlan, device):
         f = lambda a: torch.from_numpy(a).to(device)
         self.wtab, self.btab, self.utab, self.ntab = f(pl.wtab), f(pl.btab), f(pl.utab), f(pl.ntab)
         self.tensor_offsets = f(pl.st.layout.tensor_offsets)
-        self.utab_g = self.uperm = None                 # the fused tail's un-pack in gather order (plan.gather_ordered_unpack_table)
-        if not os.environ.get("SEHIP_NO_UNPACK_PERM"):
-            from .plan import gather_ordered_unpack_table
-            tg, pm = gather_ordered_unpack_table(pl.utab, pl.st.layout.tensor_offsets)
-            self.utab_g, self.uperm = f(tg), f(pm)
+        self.utab_g, self.uperm = gather_ordered_device_tables(pl.utab, pl.st.layout.tensor_offsets, f)
         self.wpack = torch.zeros(pl.n_wpack, dtype=BF16, device=device)
         self.bpack = torch.zeros(max(pl.n_bpack, 4), dtype=torch.float32, device=device)
 
 
-class DCUNetWorkspace:
+class DCUNetWorkspace(GemmWorkspace):
     """Device buffers and bound descriptors for one (batch, bins, frames)."""
 
     def __init__(self, pl: DCUNetPlan, tables: DCUNetDeviceTables, B, device):
+        super().__init__()
         self.pl, self.tb, self.B, self.device = pl, tables, B, device
-        self.generation, self.pinned, self.closed = 0, False, False
         st, n = pl.st, pl.st.n
         F0, T0 = pl.F0, pl.T0
         self.bufs = {}
@@ -532,24 +519,12 @@ class DCUNetWorkspace:
         self.bn_ticket = torch.zeros(4, dtype=torch.int32, device=device)
         self.tail_scratch = torch.zeros(int(lib.sehip_dcunet_tail_scratch_floats(B, F0, T0, st.dec_c[-1])), dtype=torch.float32,
                                         device=device)
-        self.side = None if os.environ.get("SEHIP_NO_SIDE_STREAM") else torch.cuda.Stream(device=device)
-        self._events, self._event_i, self._chain_dirty = [], 0, True
+        self.side = self._new_side_stream(device)
         self._bind()
 
-    def close(self):
-        if self.closed:
-            return
-        self.closed = True
-        lib = _lib.lib()
-        for e in self._events:
-            lib.sehip_event_destroy(e)
-        self._events = []
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    @property
+    def _layout(self):
+        return self.pl.st.layout
 
     def _bind(self):
         pl, tb, B = self.pl, self.tb, self.B
@@ -599,32 +574,7 @@ class DCUNetWorkspace:
                     w.cv2_nkt, w.cv2_nf, w.cv2_fadd, w.cv2_t0 = s.conv2
                 self.desc[name + ".wg"] = w
 
-    # ---- launches ------------------------------------------------------------------------------------
-    def gemm(self, name):
-        self._chain_dirty = True
-        call("sehip_gemm", C.byref(self.desc[name]), stream())
-
-    def _event(self):
-        if not self._events:
-            for _ in range(16):
-                e = _lib.lib().sehip_event_create()
-                if not e:
-                    raise SehipError("sehip_event_create: " + _lib.lib().sehip_last_error().decode())
-                self._events.append(e)
-        self._event_i = (self._event_i + 1) % len(self._events)
-        return self._events[self._event_i]
-
-    def wgrad(self, name):
-        """Weight gradients are side work (nothing in the backward chain consumes them): second stream, see plan.DCCRNWorkspace."""
-        main = torch.cuda.current_stream()
-        if self.side is None or torch.cuda.is_current_stream_capturing():
-            call("sehip_wgrad", C.byref(self.desc[name + ".wg"]), main.cuda_stream)
-            return
-        if self._chain_dirty:
-            call("sehip_stream_depend", self.side.cuda_stream, main.cuda_stream, self._event())
-            self._chain_dirty = False
-        call("sehip_wgrad", C.byref(self.desc[name + ".wg"]), self.side.cuda_stream)
-
+    # ---- launches (gemm, wgrad: GemmWorkspace) ---------------------------------------------------------
     def _bn_ptrs(self, pre, params, buffers, nbt):
         L = self.pl.st.layout
         pp = lambda k: params.data_ptr() + 4 * L.param_off[pre + k][0]
@@ -734,15 +684,6 @@ class DCUNetWorkspace:
             if i > 0:
                 for name in [k for k in pl.specs if k.startswith(f"enc{i}.dg")]:
                     self.gemm(name)
-        if self.side is not None and not torch.cuda.is_current_stream_capturing():
-            call("sehip_stream_depend", stream(), self.side.cuda_stream, self._event())
-        if tail is not None:
-            if tb.uperm is not None:
-                call("sehip_unpack_grad_sums_perm", ptr(self.gpack), ptr(tb.utab_g), ptr(tb.uperm), st.layout.n_params, ptr(grads), tail[2],
-                     tail[3], tail[0], tail[1], tail[4], None, stream())
-            else:
-                call("sehip_unpack_grad_sums", ptr(self.gpack), ptr(tb.utab), st.layout.n_params, ptr(grads), tail[2], tail[3], tail[0],
-                     tail[1], tail[4], None, stream())
-        else:
-            call("sehip_unpack_grad", ptr(self.gpack), ptr(tb.utab), st.layout.n_params, ptr(grads), stream())
+        self.join_side()
+        self.unpack(grads, tail)
         return grads

@@ -25,7 +25,7 @@ import torch
 from . import _lib
 from ._lib import call, ptr, stream, SehipError
 from .plan import Arena, CGemmDesc, ParamLayout, bind_chunk_table, dense_ntab, npad_of, pad_ktab, BF16
-from .plan_dcunet import Buf
+from .workspace import Buf, GemmWorkspace
 
 HEADS, NDECAY, MAX_STEPS, GN_EPS = 4, 4, 200, 1e-5
 
@@ -530,11 +530,13 @@ class DemucsDeviceTables:
             self.kup, self.kdn = f(st.kup.reshape(-1)), f(st.kdn.reshape(-1))
 
 
-class DemucsWorkspace:
+class DemucsWorkspace(GemmWorkspace):
+    event_attrs = ("_events", "_held_events")
+
     def __init__(self, st: DemucsStatic, tables: DemucsDeviceTables, B, T, device):
+        super().__init__()
         cfg = st.cfg
         self.st, self.tb, self.B, self.T, self.device = st, tables, B, T, device
-        self.generation, self.pinned, self.closed = 0, False, False
         self.Tv = cfg.valid_length(T)
         self.padl = (self.Tv - T) // 2
         self.Tin = 2 * self.Tv if cfg.resample else self.Tv
@@ -571,27 +573,9 @@ class DemucsWorkspace:
         self.attn_slabs = torch.empty(max([int(_lib.lib().sehip_dmx_attn_bwd_scratch_floats(B, lens[a["level"]], a["hid"])) for a in st.attns] + [1]),
                                       dtype=torch.float32, device=device)      # key / content gradients per query tile (LocalState backward)
         self.lstm_sync = torch.zeros(int(_lib.lib().sehip_dmx_lstm_sync_bytes()) // 4, dtype=torch.int32, device=device)   # arrival counters + time-out word
-        self._side_stream = None if os.environ.get("SEHIP_NO_SIDE_STREAM") else torch.cuda.Stream(device=device)
-        self.side = self._side_stream      # (None while the deterministic schedule is on: _select_streams)
+        self.side = self._side_stream = self._new_side_stream(device)      # (side: None while the deterministic schedule is on: _select_streams)
         self.comm = None     # third stream: early un-pack + all-reduce of finished gradient ranges (data-parallel runs only)
-        self._events, self._event_i, self._chain_dirty = [], 0, True
-        self._held_events = []
         self._bind()
-
-    def close(self):
-        if self.closed:
-            return
-        self.closed = True
-        lib = _lib.lib()
-        for e in self._events + self._held_events:
-            lib.sehip_event_destroy(e)
-        self._events, self._held_events = [], []
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _view(self, name, quad):
         b = self.bufs[name]
@@ -695,42 +679,14 @@ class DemucsWorkspace:
         else:
             call("sehip_wgrad", C.byref(self.desc[name + ".wg"]), st)
 
-    # ---- launches -----------------------------------------------------------------------------------------------------
-    def gemm(self, name):
-        self._chain_dirty = True
-        call("sehip_gemm", C.byref(self.desc[name]), stream())
+    _issue_wgrad = _launch_wgrad      # (what GemmWorkspace.wgrad() launches)
 
+    # ---- launches (gemm, wgrad: GemmWorkspace) ------------------------------------------------------------------------
     def _own_event(self, j):
         """Events that stay recorded across many launches (the round-robin pool of _event() would re-use them)."""
         while len(self._held_events) <= j:
-            e = _lib.lib().sehip_event_create()
-            if not e:
-                raise SehipError("sehip_event_create: " + _lib.lib().sehip_last_error().decode())
-            self._held_events.append(e)
+            self._held_events.append(self._new_event())
         return self._held_events[j]
-
-    def _event(self):
-        if not self._events:
-            for _ in range(16):
-                e = _lib.lib().sehip_event_create()
-                if not e:
-                    raise SehipError("sehip_event_create: " + _lib.lib().sehip_last_error().decode())
-                self._events.append(e)
-        self._event_i = (self._event_i + 1) % len(self._events)
-        return self._events[self._event_i]
-
-    def wgrad(self, name):
-        main = torch.cuda.current_stream()
-        if self.side is None or torch.cuda.is_current_stream_capturing():
-            self._launch_wgrad(name, main.cuda_stream)
-            return
-        if self._chain_dirty:
-            call("sehip_stream_depend", self.side.cuda_stream, main.cuda_stream, self._event())
-            self._chain_dirty = False
-        self._launch_wgrad(name, self.side.cuda_stream)
-
-    def _pp(self, params, name):
-        return params.data_ptr() + 4 * self.st.layout.param_off[name][0]
 
     def _norm_fwd(self, key, params, out, resid=None, add=None):
         n, j = self.st.gch[key], self.norm_idx[key]
@@ -1023,8 +979,7 @@ class DemucsWorkspace:
             if range_ready is not None and i > 0 and enc_off[i + 1] - enc_off[i] >= 0.05 * n_params and done_from == enc_off[i + 1]:
                 self._hand_over(enc_off[i], done_from, grads, range_ready)
                 done_from = enc_off[i]
-        if self.side is not None and not torch.cuda.is_current_stream_capturing():
-            call("sehip_stream_depend", stream(), self.side.cuda_stream, self._event())
+        self.join_side()
         self._unpack(0, done_from, grads, stream(), tail=tail if range_ready is None else None)
         if range_ready is not None:
             range_ready(0, done_from, torch.cuda.current_stream())

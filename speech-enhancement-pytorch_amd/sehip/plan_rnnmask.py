@@ -18,6 +18,7 @@ import torch
 from . import _lib
 from ._lib import call, ptr, stream, SehipError
 from .plan import ParamLayout, BF16
+from .workspace import Workspace
 
 BN_EPS, BN_MOMENTUM = 1e-5, 0.1
 GOLDEN = 0x9E3779B9
@@ -177,11 +178,12 @@ class RnnMaskStatic:
         return s
 
 
-class RnnMaskWorkspace:
+class RnnMaskWorkspace(Workspace):
     """Buffers and launches for inputs [B, C, F, T, 2].  `guard` > 0 (tests): every buffer sits between two bands of that many
     canary elements inside its allocation."""
 
     def __init__(self, st: RnnMaskStatic, B, T, device, guard=0):
+        super().__init__()
         cfg = st.cfg
         if B < 1 or T < 1:
             raise SehipError(f"RNNBaseSTFTMask: B={B}, T={T} must be positive")
@@ -189,7 +191,6 @@ class RnnMaskWorkspace:
         if L * cfg.num_spk > 65535 or T * L >= 2 ** 31 // (4 * cfg.Hout) or (T * L + 255) // 256 > 65535:
             raise SehipError(f"RNNBaseSTFTMask: B C = {L} steps of T = {T} rows are more than the kernels' index ranges take")
         self.st, self.cfg, self.B, self.T, self.L, self.R, self.device = st, cfg, B, T, L, T * L, device
-        self.generation, self.pinned, self.closed = 0, False, False
         self.guard, self._alloc = int(guard), {}
         self.bufs = {}
         for name, (shape, dt) in st.buffer_shapes(B, T).items():
@@ -221,12 +222,6 @@ class RnnMaskWorkspace:
     def guards_intact(self):
         """names of the buffers whose canary bands were written"""
         return [k for k, (raw, g, n) in self._alloc.items() if not (bool((raw[:g] == 7.0).all()) and bool((raw[g + n:] == 7.0).all()))]
-
-    def close(self):
-        self.closed = True
-
-    def _pp(self, params, name):
-        return params.data_ptr() + 4 * self.st.layout.param_off[name][0]
 
     def _wp(self, off):
         return self.wpack.data_ptr() + 2 * off

@@ -19,7 +19,7 @@ import torch
 from . import _lib
 from ._lib import call, ptr, stream, SehipError
 from .plan import Arena, CGemmDesc, GemmSpec, ParamLayout, bind_chunk_table, enc_entry, BF16
-from .plan_dcunet import Buf
+from .workspace import Buf, GemmWorkspace, gather_ordered_device_tables
 
 
 class TasNetConfig:
@@ -191,19 +191,15 @@ class TasNetDeviceTables:
         f = lambda a: torch.from_numpy(a).to(device)
         self.wtab, self.utab, self.ntab = f(st.wtab), f(st.utab), f(st.ntab)
         self.tensor_offsets = f(st.layout.tensor_offsets)
-        self.utab_g = self.uperm = None                 # the fused tail's un-pack in gather order (plan.gather_ordered_unpack_table)
-        if not os.environ.get("SEHIP_NO_UNPACK_PERM"):
-            from .plan import gather_ordered_unpack_table
-            tg, pm = gather_ordered_unpack_table(st.utab, st.layout.tensor_offsets)
-            self.utab_g, self.uperm = f(tg), f(pm)
+        self.utab_g, self.uperm = gather_ordered_device_tables(st.utab, st.layout.tensor_offsets, f)
         self.wpack = torch.zeros(st.n_wpack, dtype=BF16, device=device)
 
 
-class TasNetWorkspace:
+class TasNetWorkspace(GemmWorkspace):
     def __init__(self, st: TasNetStatic, tables: TasNetDeviceTables, M, T, device):
+        super().__init__()
         cfg = st.cfg
         self.st, self.tb, self.M, self.T, self.device = st, tables, M, T, device
-        self.generation, self.pinned, self.closed = 0, False, False
         if T < cfg.L:
             raise SehipError(f"ConvTasNet: a clip of {T} samples is shorter than one analysis window (L={cfg.L})")
         self.K = K = (T - cfg.L) // (cfg.L // 2) + 1
@@ -236,25 +232,8 @@ class TasNetWorkspace:
                                          dtype=torch.float32, device=device)
         self.wav = None
         self._one_clear, self._bwd_clean = not os.environ.get("SEHIP_CTN_TORCH_ZEROS"), False
-        self._side_stream = None if os.environ.get("SEHIP_NO_SIDE_STREAM") else torch.cuda.Stream(device=device)
-        self.side = self._side_stream      # (None while the deterministic schedule is on: forward())
-        self._events, self._event_i, self._chain_dirty = [], 0, True
+        self.side = self._side_stream = self._new_side_stream(device)      # (side: None while the deterministic schedule is on: forward())
         self._bind()
-
-    def close(self):
-        if self.closed:
-            return
-        self.closed = True
-        lib = _lib.lib()
-        for e in self._events:
-            lib.sehip_event_destroy(e)
-        self._events = []
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _bind(self):
         st, tb, M, K = self.st, self.tb, self.M, self.K
@@ -294,33 +273,6 @@ class TasNetWorkspace:
         lib_ = _lib.lib()
         self.fused_gln = (st.cfg.norm_type == "gLN" and not os.environ.get("SEHIP_CTN_NO_FUSED_GLN") and len(st.blocks) > 0 and
                           all(int(lib_.sehip_gemm_takes_gln_stats(C.byref(self.desc[f"b{i}.in.fwd"]))) == 1 for i in range(len(st.blocks))))
-
-    def gemm(self, name):
-        self._chain_dirty = True
-        call("sehip_gemm", C.byref(self.desc[name]), stream())
-
-    def _event(self):
-        if not self._events:
-            for _ in range(16):
-                e = _lib.lib().sehip_event_create()
-                if not e:
-                    raise SehipError("sehip_event_create: " + _lib.lib().sehip_last_error().decode())
-                self._events.append(e)
-        self._event_i = (self._event_i + 1) % len(self._events)
-        return self._events[self._event_i]
-
-    def wgrad(self, name):
-        main = torch.cuda.current_stream()
-        if self.side is None or torch.cuda.is_current_stream_capturing():
-            call("sehip_wgrad", C.byref(self.desc[name + ".wg"]), main.cuda_stream)
-            return
-        if self._chain_dirty:
-            call("sehip_stream_depend", self.side.cuda_stream, main.cuda_stream, self._event())
-            self._chain_dirty = False
-        call("sehip_wgrad", C.byref(self.desc[name + ".wg"]), self.side.cuda_stream)
-
-    def _pp(self, params, name):
-        return params.data_ptr() + 4 * self.st.layout.param_off[name][0]
 
     def forward(self, wav, params):
         """wav [M, ac, T] fp32 on device -> self.out [M, C, ac, T]."""
@@ -390,7 +342,7 @@ class TasNetWorkspace:
         gp = lambda off: self.gpack.data_ptr() + 4 * off
         nb = len(st.blocks)
         net = "separator.network."
-        if not getattr(self, "_bwd_clean", False):      # (a second backward pass over the same forward, or the torch-fill switch)
+        if not self._bwd_clean:      # (a second backward pass over the same forward, or the torch-fill switch)
             self.gpack.zero_()
             self.bsums.zero_()
         self._bwd_clean = False
@@ -430,15 +382,6 @@ class TasNetWorkspace:
         self.gemm("bott.dg")
         call("sehip_ctn_encoder_bwd", ptr(self.wav), ptr(self.w), b["dcln"].ptr, ptr(self.dw_dec), pp(net + "0.gamma"), M,
              cfg.audio_channels, self.T, N, cfg.L, gp(st.enc_g_off), ptr(self.codec_scratch), stream())
-        if self.side is not None and not torch.cuda.is_current_stream_capturing():
-            call("sehip_stream_depend", stream(), self.side.cuda_stream, self._event())
-        if tail is not None:         # FlatOptimizer's accumulators: the un-pack also takes the clipping norm / metric sums (plan.DCCRNWorkspace.backward)
-            if tb.uperm is not None:
-                call("sehip_unpack_grad_sums_perm", ptr(self.gpack), ptr(tb.utab_g), ptr(tb.uperm), st.layout.n_params, ptr(grads), tail[2],
-                     tail[3], tail[0], tail[1], tail[4], None, stream())
-            else:
-                call("sehip_unpack_grad_sums", ptr(self.gpack), ptr(tb.utab), st.layout.n_params, ptr(grads), tail[2], tail[3], tail[0],
-                     tail[1], tail[4], None, stream())
-        else:
-            call("sehip_unpack_grad", ptr(self.gpack), ptr(tb.utab), st.layout.n_params, ptr(grads), stream())
+        self.join_side()
+        self.unpack(grads, tail)
         return grads

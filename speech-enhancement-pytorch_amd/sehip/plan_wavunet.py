@@ -14,7 +14,6 @@ Everything else is csrc/wavunet.hip: the first layer straight from the fp32 wave
 forward / backward), the same fused with the align-corners x2 linear upsampling (the activated tensor of a decoder / middle layer is
 never stored), the upsampling's adjoint as a gather, and the ``cat + 1x1 + tanh`` head.
 """
-import ctypes as C
 import os
 
 import numpy as np
@@ -23,7 +22,7 @@ import torch
 from . import _lib
 from ._lib import call, ptr, stream, SehipError
 from .plan import Arena, CGemmDesc, ParamLayout, bind_chunk_table, dense_ntab, npad_of, pad_ktab, BF16
-from .plan_dcunet import Buf
+from .workspace import Buf, GemmWorkspace
 
 BN_EPS, BN_MOMENTUM, ENC_TAPS, DEC_TAPS = 1e-5, 0.1, 15, 5
 
@@ -257,8 +256,9 @@ def valid_lengths(T, n):
     return lo, hi
 
 
-class WavUnetWorkspace:
+class WavUnetWorkspace(GemmWorkspace):
     def __init__(self, st: WavUnetStatic, tables: WavUnetDeviceTables, B, T, device):
+        super().__init__()
         cfg = st.cfg
         n = cfg.n
         if T % 2 ** n or T // 2 ** n < 2:
@@ -269,7 +269,6 @@ class WavUnetWorkspace:
         if B < 1 or B > 65535:
             raise SehipError(f"WavUnet: batch size B={B} must be in 1 .. 65535")
         self.st, self.tb, self.B, self.T, self.device = st, tables, B, T, device
-        self.generation, self.pinned, self.closed = 0, False, False
         self.lens = [T >> l for l in range(n + 1)]
         lib = _lib.lib()
         self.bufs = {}
@@ -288,25 +287,8 @@ class WavUnetWorkspace:
         self.wav = None
         self.training = True
         self._bwd_clean = False
-        self._side_stream = None if os.environ.get("SEHIP_NO_SIDE_STREAM") else torch.cuda.Stream(device=device)
-        self.side = self._side_stream
-        self._events, self._event_i, self._chain_dirty = [], 0, True
+        self.side = self._side_stream = self._new_side_stream(device)
         self._bind()
-
-    def close(self):
-        if self.closed:
-            return
-        self.closed = True
-        lib = _lib.lib()
-        for e in self._events:
-            lib.sehip_event_destroy(e)
-        self._events = []
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _view(self, name, pair):
         b = self.bufs[name]
@@ -351,33 +333,7 @@ class WavUnetWorkspace:
                 w.dst[0].ptr = gb.ptr
                 self.desc[name + ".wg"] = w
 
-    # ---- launches -----------------------------------------------------------------------------------------------------
-    def gemm(self, name):
-        self._chain_dirty = True
-        call("sehip_gemm", C.byref(self.desc[name]), stream())
-
-    def _event(self):
-        if not self._events:
-            for _ in range(16):
-                e = _lib.lib().sehip_event_create()
-                if not e:
-                    raise SehipError("sehip_event_create: " + _lib.lib().sehip_last_error().decode())
-                self._events.append(e)
-        self._event_i = (self._event_i + 1) % len(self._events)
-        return self._events[self._event_i]
-
-    def wgrad(self, name):
-        if self.side is None or torch.cuda.is_current_stream_capturing():
-            call("sehip_wgrad", C.byref(self.desc[name + ".wg"]), stream())
-            return
-        if self._chain_dirty:
-            call("sehip_stream_depend", self.side.cuda_stream, stream(), self._event())
-            self._chain_dirty = False
-        call("sehip_wgrad", C.byref(self.desc[name + ".wg"]), self.side.cuda_stream)
-
-    def _pp(self, params, name):
-        return params.data_ptr() + 4 * self.st.layout.param_off[name][0]
-
+    # ---- launches (gemm, wgrad: GemmWorkspace) ------------------------------------------------------------------------
     def _norm_coef(self, key, params, buffers, nbt, training):
         """batch (training) or running (eval) statistics of layer `key` -> its coefficient records"""
         nm, L = self.st.norms[key], self.st.layout
@@ -467,8 +423,7 @@ class WavUnetWorkspace:
                 self.gemm(k + ".dg")
         call("sehip_wun_enc0_wgrad", b["e0.dy"].ptr, ptr(self.wav), B, T, c0, gp(st.enc0_goff), gp(st.enc0_goff + ENC_TAPS * c0),
              ptr(self.enc0_scratch), stream())
-        if self.side is not None and not torch.cuda.is_current_stream_capturing():
-            call("sehip_stream_depend", stream(), self.side.cuda_stream, self._event())
+        self.join_side()
         np_ = st.layout.n_params
         if tail is not None:      # FlatOptimizer's accumulators: the un-pack also takes the clipping norm / metric sums
             call("sehip_unpack_grad1_sums", ptr(self.gpack), ptr(tb.utab1), np_, ptr(grads), tail[2], tail[3], tail[0], tail[1], tail[4],

@@ -422,8 +422,7 @@ class Solver(object):
         self.model.workspace(mixture.shape[0], mixture.shape[-1]).pinned = True  # all buffers exist before capture and stay
         self.optimizer._ensure_state()
         self.model.flat_grads
-        if self.model._anchor is None or self.model._anchor.device != mixture.device:
-            self.model._anchor = torch.zeros(1, device=mixture.device, requires_grad=True)
+        self.model._grad_anchor(mixture.device)      # exists before the capture
         mix, src = mixture.clone(), sources.clone()
         if self._pit_applies(src):
             from . import loss as loss_module

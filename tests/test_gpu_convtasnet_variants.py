@@ -42,20 +42,22 @@ DEFAULT_SEQUENCE = DEFAULT_HEAD + 14 * DEFAULT_BLOCK_FWD + DEFAULT_MID + 14 * DE
 
 
 def record_calls(fn):
-    """entry-point names that fn() issues through sehip.plan_tasnet.call"""
-    from sehip import plan_tasnet
+    """entry-point names that fn() issues through sehip.plan_tasnet.call and, for the products, the weight gradients and the un-pack,
+    through sehip.workspace.call"""
+    from sehip import plan_tasnet, workspace
     names, real = [], plan_tasnet.call
+    assert workspace.call is real
 
     def spy(name, *a):
         names.append(name)
         return real(name, *a)
 
-    plan_tasnet.call = spy
+    plan_tasnet.call = workspace.call = spy
     try:
         fn()
         torch.cuda.synchronize()
     finally:
-        plan_tasnet.call = real
+        plan_tasnet.call = workspace.call = real
     return names
 
 

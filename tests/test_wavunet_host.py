@@ -252,8 +252,10 @@ def test_plan_on_the_emulated_c_abi(tag, monkeypatch):
     fx = fixture(tag)
     emu = Emulator()
     monkeypatch.setenv("SEHIP_NO_SIDE_STREAM", "1")
-    monkeypatch.setattr(P, "call", emu)
-    monkeypatch.setattr(P, "stream", lambda: None)
+    from sehip import workspace as W
+    for mod in (P, W):            # (gemm() and wgrad() launch from the workspace base)
+        monkeypatch.setattr(mod, "call", emu)
+        monkeypatch.setattr(mod, "stream", lambda: None)
     model = WavUnet(**model_kw(tag))
     model.load_state_dict(fx["sd"])
     cpu = torch.device("cpu")
