@@ -760,7 +760,20 @@ int sehip_wun_out_bwd(const float* dout, const float* out, const void* z, const 
  *      bn_apply      : z = scale y + shift with coef [C][4] of sehip_wun_bn_finalize (BatchNorm1d without an activation)
  *      bn_bwd_apply  : dy = gamma rstd (dz - mean(dz) - xhat mean(dz xhat))
  *      mask_fwd      : out fp32 [B][S][C][F][T][2] = mask[(t, b C + c)][s F + f] x[b][c][f][t][:], mask bf16 [T][B C][SFp]
- *      mask_bwd      : dpre bf16 [T][B C][SFp] = (mask > 0) (dout_re x_re + dout_im x_im); columns S F .. SFp-1 are not touched */
+ *      mask_bwd      : dpre bf16 [T][B C][SFp] = (mask > 0) (dout_re x_re + dout_im x_im); columns S F .. SFp-1 are not touched
+ *
+ *      mel-rnn (src/model/mel_rnn.py:8-114, MelRNN at n_mels = 0) runs on the entries above plus five:
+ *      elman_fwd     : one layer of the bias-free tanh cell, L launches, grid (ceil(H / 64), D, ceil(Bn / 16)): the four waves of a
+ *                      workgroup take four 16-unit blocks.  h(l) = tanh(pre(l) + h(l-1) W_hh^T); pre fp32 [Bn][L][D][H], whh bf16
+ *                      [D][H][H]; writes hs bf16 [Bn][L][D H] (output and next step's operand) and state fp32 [Bn][L][D H], the same h
+ *                      unrounded.  Direction 1 walks the steps backwards.  L = 1 launches no product.  No dropout arguments (MelRNN has
+ *                      none; rnn-stft-mask's Elman cell would still need them)
+ *      elman_bwd     : dG bf16 [Bn][L][D][H], dG(l) = (dhs(l) + dG(l+1) W_hh) (1 - state(l)^2); whhT bf16 [D][H][H] = W_hh transposed,
+ *                      dhs bf16 [Bn][L][D H].  dG(l+1) is read back as stored: no carried scratch
+ *      gemm_nt_head  : sehip_rsm_gemm_nt with the head's two other epilogues.  3: C bf16 = sigmoid(. + bias[n]); 4: C bf16 = . where
+ *                      gate[m][n] > 0, else 0 (gate bf16 [M][ldg], ldg >= N: a stored ReLU output).  Any other epilogue is refused
+ *      mask_bwd_sigmoid : dpre bf16 [T][B C][SFp] = m (1 - m) (dout_re x_re + dout_im x_im), m the stored bf16 mask; columns
+ *                      S F .. SFp-1 are not touched */
 long sehip_rsm_sum_scratch_floats(long rows, int C);
 int sehip_rsm_counter_next(void* counter, void* used, void* stream);
 int sehip_rsm_features(const float* x, int RC, int F, int T, int Fp, void* feat, void* stream);
@@ -780,6 +793,12 @@ int sehip_rsm_bn_bwd_apply(const void* dz, const void* y, const float* coef, con
 int sehip_rsm_mask_fwd(const void* mask, const float* x, int B, int Cn, int S, int F, int T, int SFp, float* out, void* stream);
 int sehip_rsm_mask_bwd(const float* dout, const float* x, const void* mask, int B, int Cn, int S, int F, int T, int SFp, void* dpre,
                        void* stream);
+int sehip_rsm_elman_fwd(const float* pre, const void* whh, void* hs, float* state, int Bn, int L, int H, int D, void* stream);
+int sehip_rsm_elman_bwd(const void* whhT, const float* state, const void* dhs, void* dG, int Bn, int L, int H, int D, void* stream);
+int sehip_rsm_gemm_nt_head(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epilogue, const float* bias,
+                           const void* gate, int ldg, void* C, int ldc, void* stream);
+int sehip_rsm_mask_bwd_sigmoid(const float* dout, const float* x, const void* mask, int B, int Cn, int S, int F, int T, int SFp, void* dpre,
+                               void* stream);
 
 /* ---- hearing-aid back end (src/audio.py:33-61 amplify_torch = NAL-R FIR, compressor, tanh; csrc/hearing_aid.hip).  All rows are
  *      dense fp32 [rows][n], 1 <= rows <= 65535, 1 <= n <= 2^30; arguments are validated before any HIP call; nothing synchronises,

@@ -205,6 +205,10 @@ _PROTOS = {
     "sehip_rsm_bn_bwd_apply": [P, P, P, P, L, I, P, P],
     "sehip_rsm_mask_fwd": [P, P, I, I, I, I, I, I, P, P],
     "sehip_rsm_mask_bwd": [P, P, P, I, I, I, I, I, I, P, P],
+    "sehip_rsm_elman_fwd": [P, P, P, P, I, I, I, I, P],
+    "sehip_rsm_elman_bwd": [P, P, P, P, I, I, I, I, P],
+    "sehip_rsm_gemm_nt_head": [P, I, P, I, I, I, I, I, P, P, I, P, I, P],
+    "sehip_rsm_mask_bwd_sigmoid": [P, P, P, I, I, I, I, I, I, P, P],
     "sehip_ha_fir_fwd": [P, L, L, P, I, I, P, P, P],
     "sehip_ha_fir_adj": [P, L, L, P, I, I, P, P, P],
     "sehip_ha_compressor_ws_doubles": [L, L, I],

@@ -14,6 +14,11 @@
 // Every sum has one owner and a fixed order: no atomics, no split-K, two runs are bit-identical.
 //
 // Recurrence.  One launch per step, grid (H / 16, directions, ceil(rows / 16)): no persistent kernel, no hand-off, no spin.
+//
+// mel-rnn (src/model/mel_rnn.py:8-114, MelRNN at n_mels = 0) is the same pipeline with three more cells of arithmetic: the Elman
+// recurrence (rsm_elman_step_*: one gate, so a workgroup's four waves take four 16-unit blocks, grid (ceil(H / 64), directions,
+// ceil(rows / 16))), a head of Linear + ReLU + Linear + Sigmoid (two more epilogues of rsm_gemm_nt_kernel) and a mask backward that
+// carries the sigmoid's derivative.
 #include "common.h"
 
 namespace {
@@ -86,10 +91,12 @@ __global__ __launch_bounds__(256) void rsm_pack_w_kernel(const float* __restrict
 
 // ---- C = A B^T ------------------------------------------------------------------------------------------------------------------------
 // A [M][lda], B [N][ldb] bf16, K a multiple of 8 (chunks beyond K read as zero), rows beyond M / N are neither read nor written.
-// EPI 0: fp32 C; 1: bf16 C; 2: bf16 max(C + bias[n], 0).  Workgroup = 64 x 64 of C, wave w its rows 16 w .. 16 w + 15.
+// EPI 0: fp32 C; 1: bf16 C; 2: bf16 max(C + bias[n], 0); 3: bf16 sigmoid(C + bias[n]); 4: bf16 C where gate[m][n] > 0, else 0 (gate bf16
+// [M][ldg]: a stored ReLU output).  Workgroup = 64 x 64 of C, wave w its rows 16 w .. 16 w + 15.
 template <int EPI>
 __global__ __launch_bounds__(256) void rsm_gemm_nt_kernel(const bf16_raw* __restrict__ A, int lda, const bf16_raw* __restrict__ B, int ldb, int M, int N,
-                                                          int K, const float* __restrict__ bias, void* __restrict__ Cout, int ldc) {
+                                                          int K, const float* __restrict__ bias, void* __restrict__ Cout, int ldc,
+                                                          const bf16_raw* __restrict__ gate = nullptr, int ldg = 0) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, i = lane & 15, kg = lane >> 4;
     const int m0 = blockIdx.y * 64 + 16 * w, n0 = blockIdx.x * 64;
     if (m0 >= M) return;
@@ -129,7 +136,9 @@ __global__ __launch_bounds__(256) void rsm_gemm_nt_kernel(const bf16_raw* __rest
             const long o = (long)m * ldc + n;
             if (EPI == 0) ((float*)Cout)[o] = acc[j][r];
             else if (EPI == 1) ((bf16_raw*)Cout)[o] = f2bf(acc[j][r]);
-            else ((bf16_raw*)Cout)[o] = f2bf(fmaxf(acc[j][r] + bias[n], 0.f));
+            else if (EPI == 2) ((bf16_raw*)Cout)[o] = f2bf(fmaxf(acc[j][r] + bias[n], 0.f));
+            else if (EPI == 3) ((bf16_raw*)Cout)[o] = f2bf(rsm_sigm(acc[j][r] + bias[n]));
+            else ((bf16_raw*)Cout)[o] = bf2f(gate[(long)m * ldg + n]) > 0.f ? f2bf(acc[j][r]) : (bf16_raw)0;
         }
     }
 }
@@ -371,6 +380,71 @@ __global__ __launch_bounds__(256) void rsm_gru_step_bwd_kernel(const float* __re
     dG[g0 + 3 * H] = f2bf(dpn * gr);
 }
 
+// ---- Elman cell, one step: h(t) = tanh(pre(t) + h(t-1) W_hh^T).  pre fp32 [Bn][L][D][H] = x W_ih^T (no bias), whh bf16 [D][H][H], hs bf16
+// [Bn][L][D H] (output and next step's operand), hf fp32 [Bn][L][D H] the same h unrounded (backward reads it).  One gate: wave w of a
+// workgroup owns the 16 hidden units 64 blockIdx.x + 16 w .. + 15 (waves beyond H leave: H = 32 and 96 end in a ragged block), takes
+// all of K itself and writes its accumulator fragment (lane (m, ug): rows 4 ug .. 4 ug + 3 of unit m) straight out: no LDS, no barrier.
+__global__ __launch_bounds__(256) void rsm_elman_step_fwd_kernel(const float* __restrict__ pre, const bf16_raw* __restrict__ whh, bf16_raw* __restrict__ hs,
+                                                                 float* __restrict__ hf, int Bn, int L, int H, int D, int s) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, m = lane & 15, ug = lane >> 4;
+    const int dir = blockIdx.y, u0 = blockIdx.x * 64 + 16 * w, bt = blockIdx.z * 16;
+    if (u0 >= H) return;
+    const int t = dir ? L - 1 - s : s, tp = dir ? t + 1 : t - 1;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    if (s > 0) {
+        const int brow = bt + m;
+        const bf16_raw* hp = hs + ((long)(brow < Bn ? brow : Bn - 1) * L + tp) * D * H + dir * H + 8 * ug;
+        const bf16_raw* wp = whh + ((long)dir * H + u0 + m) * H + 8 * ug;
+        for (int k0 = 0; k0 < H; k0 += 32) {
+            uint4 av = *reinterpret_cast<const uint4*>(hp + k0);
+            if (brow >= Bn) av = make_uint4(0, 0, 0, 0);
+            const uint4 bv = *reinterpret_cast<const uint4*>(wp + k0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, av), __builtin_bit_cast(bf16x8, bv), acc, 0, 0, 0);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int b = bt + 4 * ug + r;
+        if (b >= Bn) continue;
+        const long o = ((long)b * L + t) * D * H + dir * H + u0 + m;
+        const float h = tanhf(pre[o] + acc[r]);
+        hf[o] = h;
+        hs[o] = f2bf(h);
+    }
+}
+
+// Backward step: dpre(t) = (dhs(t) + dpre(t+1) W_hh) (1 - h(t)^2), dpre(t+1) read back as the bf16 dG the previous launch stored (nothing
+// is carried beside it).  whhT bf16 [D][H][H] (W_hh transposed), dhs bf16 [Bn][L][D H], dG bf16 [Bn][L][D][H].
+__global__ __launch_bounds__(256) void rsm_elman_step_bwd_kernel(const bf16_raw* __restrict__ whhT, const float* __restrict__ hf,
+                                                                 const bf16_raw* __restrict__ dhs, bf16_raw* __restrict__ dG, int Bn, int L, int H, int D,
+                                                                 int s) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, m = lane & 15, ug = lane >> 4;
+    const int dir = blockIdx.y, u0 = blockIdx.x * 64 + 16 * w, bt = blockIdx.z * 16;
+    if (u0 >= H) return;
+    const int t = dir ? s : L - 1 - s;
+    const int tn = dir ? t - 1 : t + 1;         // the step after t in forward order (the previous launch)
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    if (s > 0) {
+        const int brow = bt + m;
+        const bf16_raw* ap = dG + ((long)(brow < Bn ? brow : Bn - 1) * L + tn) * D * H + dir * H + 8 * ug;
+        const bf16_raw* wp = whhT + ((long)dir * H + u0 + m) * H + 8 * ug;
+        for (int k0 = 0; k0 < H; k0 += 32) {
+            uint4 av = *reinterpret_cast<const uint4*>(ap + k0);
+            if (brow >= Bn) av = make_uint4(0, 0, 0, 0);
+            const uint4 bv = *reinterpret_cast<const uint4*>(wp + k0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, av), __builtin_bit_cast(bf16x8, bv), acc, 0, 0, 0);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int b = bt + 4 * ug + r;
+        if (b >= Bn) continue;
+        const long o = ((long)b * L + t) * D * H + dir * H + u0 + m;
+        const float h = hf[o];
+        dG[o] = f2bf((bf2f(dhs[o]) + acc[r]) * (1.f - h * h));
+    }
+}
+
 // ---- column sums over rows of [rows][C] bf16, two fixed-order stages.  Stage one: 256 rows per workgroup, 64 columns x 4 row lanes;
 // part [chunks][2][C].  MODE 0: (sum a, 0);  MODE 1: (sum a, sum a xhat), xhat = (y - mean) rstd from coef [C][4] = (scale, shift, mean, rstd)
 #define RSM_SUM_ROWS 256
@@ -463,7 +537,9 @@ __global__ __launch_bounds__(256) void rsm_mask_fwd_kernel(const bf16_raw* __res
         }
     }
 }
-// dpre bf16 [T][RC][SFp] = (mask > 0) (dout_re x_re + dout_im x_im): the gradient in front of the head's ReLU; padded columns untouched
+// dpre bf16 [T][RC][SFp] = (mask > 0) (dout_re x_re + dout_im x_im): the gradient in front of the head's ReLU; padded columns untouched.
+// SIGMOID: the head ends in a sigmoid instead, dpre = m (1 - m) (dout_re x_re + dout_im x_im) with m the stored bf16 mask.
+template <bool SIGMOID>
 __global__ __launch_bounds__(256) void rsm_mask_bwd_kernel(const float2* __restrict__ dout, const float2* __restrict__ x, const bf16_raw* __restrict__ mask,
                                                            int Cn, int S, int F, int T, int RC, int SFp, bf16_raw* __restrict__ dpre) {
     __shared__ float tile[32][33];      // [f][t]
@@ -487,7 +563,9 @@ __global__ __launch_bounds__(256) void rsm_mask_bwd_kernel(const float2* __restr
         const int t = t0 + b + 8 * i, f = f0 + a;
         if (t < T && f < F) {
             const long o = ((long)t * RC + rc) * SFp + sp * F + f;
-            dpre[o] = bf2f(mask[o]) > 0.f ? f2bf(tile[a][b + 8 * i]) : (bf16_raw)0;
+            const float mk = bf2f(mask[o]);
+            if (SIGMOID) dpre[o] = f2bf(mk * (1.f - mk) * tile[a][b + 8 * i]);
+            else dpre[o] = mk > 0.f ? f2bf(tile[a][b + 8 * i]) : (bf16_raw)0;
         }
     }
 }
@@ -553,6 +631,22 @@ extern "C" int sehip_rsm_gemm_nt(const void* A, int lda, const void* B, int ldb,
     return 0;
 }
 
+extern "C" int sehip_rsm_gemm_nt_head(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epilogue, const float* bias,
+                                      const void* gate, int ldg, void* C, int ldc, void* stream) {
+    SEHIP_REQUIRE(A && B && C, "rsm_gemm_nt_head: null pointer");
+    SEHIP_REQUIRE(M >= 1 && N >= 1 && K >= 8 && K % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 && lda >= K && ldb >= K && ldc >= N,
+                  "rsm_gemm_nt_head: M=%d N=%d K=%d lda=%d ldb=%d ldc=%d (K and the operand strides are multiples of 8)", M, N, K, lda, ldb, ldc);
+    SEHIP_REQUIRE((M + 63) / 64 <= 65535, "rsm_gemm_nt_head: M=%d: more than 65535 row tiles", M);
+    SEHIP_REQUIRE((epilogue == 3 && bias) || (epilogue == 4 && gate && ldg >= N),
+                  "rsm_gemm_nt_head: epilogue %d (3: bias + sigmoid, needs bias; 4: gated by a stored ReLU output, needs gate and ldg=%d >= N)", epilogue, ldg);
+    const dim3 grid((N + 63) / 64, (M + 63) / 64);
+    const bf16_raw *a = (const bf16_raw*)A, *b = (const bf16_raw*)B;
+    if (epilogue == 3) rsm_gemm_nt_kernel<3><<<grid, 256, 0, (hipStream_t)stream>>>(a, lda, b, ldb, M, N, K, bias, C, ldc, nullptr, 0);
+    else rsm_gemm_nt_kernel<4><<<grid, 256, 0, (hipStream_t)stream>>>(a, lda, b, ldb, M, N, K, nullptr, C, ldc, (const bf16_raw*)gate, ldg);
+    SEHIP_CHECK_LAUNCH("rsm_gemm_nt_head");
+    return 0;
+}
+
 extern "C" int sehip_rsm_gemm_tn(const void* A, int lda, const void* X, int ldx, int M, int N, int K, int L, int shift, float* dW, int ldw,
                                  void* stream) {
     SEHIP_REQUIRE(A && X && dW, "rsm_gemm_tn: null pointer");
@@ -599,6 +693,26 @@ extern "C" int sehip_rsm_rnn_bwd(int gru, const float* gates, const void* whhT, 
             rsm_lstm_step_bwd_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(gates, (const bf16_raw*)whhT, state, (const bf16_raw*)dhs, (bf16_raw*)dG, carry, Bn, L, H, D, s, dp);
     }
     SEHIP_CHECK_LAUNCH("rsm_rnn_bwd");
+    return 0;
+}
+
+extern "C" int sehip_rsm_elman_fwd(const float* pre, const void* whh, void* hs, float* state, int Bn, int L, int H, int D, void* stream) {
+    if (int e = check_rnn("rsm_elman_fwd", Bn, L, H, D)) return e;
+    SEHIP_REQUIRE(pre && whh && hs && state, "rsm_elman_fwd: null pointer");
+    const dim3 grid((H + 63) / 64, D, (Bn + 15) / 16);
+    for (int s = 0; s < L; ++s)
+        rsm_elman_step_fwd_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(pre, (const bf16_raw*)whh, (bf16_raw*)hs, state, Bn, L, H, D, s);
+    SEHIP_CHECK_LAUNCH("rsm_elman_fwd");
+    return 0;
+}
+
+extern "C" int sehip_rsm_elman_bwd(const void* whhT, const float* state, const void* dhs, void* dG, int Bn, int L, int H, int D, void* stream) {
+    if (int e = check_rnn("rsm_elman_bwd", Bn, L, H, D)) return e;
+    SEHIP_REQUIRE(whhT && state && dhs && dG, "rsm_elman_bwd: null pointer");
+    const dim3 grid((H + 63) / 64, D, (Bn + 15) / 16);
+    for (int s = 0; s < L; ++s)
+        rsm_elman_step_bwd_kernel<<<grid, 256, 0, (hipStream_t)stream>>>((const bf16_raw*)whhT, state, (const bf16_raw*)dhs, (bf16_raw*)dG, Bn, L, H, D, s);
+    SEHIP_CHECK_LAUNCH("rsm_elman_bwd");
     return 0;
 }
 
@@ -657,9 +771,19 @@ extern "C" int sehip_rsm_mask_bwd(const float* dout, const float* x, const void*
                                   void* stream) {
     if (int e = check_mask("rsm_mask_bwd", B, Cn, S, F, T, SFp)) return e;
     SEHIP_REQUIRE(dout && x && mask && dpre, "rsm_mask_bwd: null pointer");
-    rsm_mask_bwd_kernel<<<dim3((T + 31) / 32, (F + 31) / 32, B * Cn * S), 256, 0, (hipStream_t)stream>>>((const float2*)dout, (const float2*)x,
-                                                                                                      (const bf16_raw*)mask, Cn, S, F, T, B * Cn, SFp,
-                                                                                                      (bf16_raw*)dpre);
+    rsm_mask_bwd_kernel<false><<<dim3((T + 31) / 32, (F + 31) / 32, B * Cn * S), 256, 0, (hipStream_t)stream>>>((const float2*)dout, (const float2*)x,
+                                                                                                             (const bf16_raw*)mask, Cn, S, F, T, B * Cn,
+                                                                                                             SFp, (bf16_raw*)dpre);
     SEHIP_CHECK_LAUNCH("rsm_mask_bwd");
+    return 0;
+}
+extern "C" int sehip_rsm_mask_bwd_sigmoid(const float* dout, const float* x, const void* mask, int B, int Cn, int S, int F, int T, int SFp, void* dpre,
+                                          void* stream) {
+    if (int e = check_mask("rsm_mask_bwd_sigmoid", B, Cn, S, F, T, SFp)) return e;
+    SEHIP_REQUIRE(dout && x && mask && dpre, "rsm_mask_bwd_sigmoid: null pointer");
+    rsm_mask_bwd_kernel<true><<<dim3((T + 31) / 32, (F + 31) / 32, B * Cn * S), 256, 0, (hipStream_t)stream>>>((const float2*)dout, (const float2*)x,
+                                                                                                            (const bf16_raw*)mask, Cn, S, F, T, B * Cn,
+                                                                                                            SFp, (bf16_raw*)dpre);
+    SEHIP_CHECK_LAUNCH("rsm_mask_bwd_sigmoid");
     return 0;
 }

@@ -11,6 +11,10 @@ Launch list of one layer: the input projection of all steps and both directions 
 (sehip_rsm_rnn_fwd).  Backward: L step launches, per direction the two weight-gradient products (sehip_rsm_gemm_tn, the recurrent one
 with a row shift of -+1), and the input gradient of both directions in one product.  Weight gradients land in the flat gradient
 buffer in the parameters' own layout: there is no packed-gradient buffer and no un-packing table for this model.
+
+That per-layer loop, its weight copies and its buffers are the recurrent stack (stack_arena / stack_pack_launches / stack_buffer_shapes,
+RnnStackWorkspace.stack_forward / stack_backward), parametrised by the cell and shared with mel-rnn (sehip/plan_melrnn.py), which adds the
+Elman cell (sehip_rsm_elman_fwd / _bwd).
 """
 import numpy as np
 import torch
@@ -85,6 +89,8 @@ class RnnMaskConfig:
         self.rnn_hidden, self.rnn_layer, self.rnn_type, self.drop_out, self.bidirectional = rnn_hidden, rnn_layer, rnn_type, float(drop_out), bidirectional
         self.gru = rnn_type == "gru"
         self.G = 3 if self.gru else 4
+        self.GB = 4                                  # blocks of H per direction in dG and the transposed W_ih (the GRU's fourth: r d pre_n)
+        self.has_dropout = True                      # a dropped-out copy hd{k} of every layer's output but the last
         self.D = 2 if bidirectional else 1
         self.H = rnn_hidden
         self.Hout = self.D * self.H
@@ -114,23 +120,66 @@ class RnnMaskConfig:
         return out
 
 
+# ---- the recurrent stack: the part rnn-stft-mask and mel-rnn share.  A configuration names its cell through G (gates of H in the
+# pre-activations: 4 lstm, 3 gru, 1 Elman), GB (blocks of H per direction in dG: 4, 4, 1), gru and, for the Elman cell, elman ----------------
+def stack_arena(cfg, w, off):
+    """adds the stack's bf16 weight copies to the arena map w ((layer, what) -> element offset) from offset `off`; returns the next offset"""
+    G, GB, H, D = cfg.G, cfg.GB, cfg.H, cfg.D
+    for k in range(cfg.rnn_layer):
+        kin, kp = cfg.layer_in(k)
+        for what, n in (("ih", D * G * H * kp),          # [D G H][kp]      operand of the input projection
+                        ("ihT", kp * D * GB * H),        # [kp][D][GB][H]   operand of the input gradient (GRU: block 3 stays zero)
+                        ("hh", D * G * H * H),           # [D][G H][H]      forward steps
+                        ("hhT", D * H * G * H)):         # [D][H][G H]      backward steps
+            w[(k, what)] = off
+            off += n
+    return off
+
+
+def stack_pack_launches(cfg, w):
+    """[(parameter name, row offset in it, N, K, transpose, ld, arena offset)]: the stack's sehip_rsm_pack_w calls of one step"""
+    G, GB, H, D = cfg.G, cfg.GB, cfg.H, cfg.D
+    out = []
+    for k in range(cfg.rnn_layer):
+        kin, kp = cfg.layer_in(k)
+        for d, sfx in enumerate(("", "_reverse")[:D]):
+            ih, hh = f"rnn.weight_ih_l{k}{sfx}", f"rnn.weight_hh_l{k}{sfx}"
+            out.append((ih, 0, G * H, kin, 0, kp, w[(k, "ih")] + d * G * H * kp))
+            out.append((hh, 0, G * H, H, 0, H, w[(k, "hh")] + d * G * H * H))
+            out.append((hh, 0, G * H, H, 1, G * H, w[(k, "hhT")] + d * H * G * H))
+            if k > 0:
+                out.append((ih, 0, G * H, kin, 1, D * GB * H, w[(k, "ihT")] + d * GB * H))
+    return out
+
+
+def stack_buffer_shapes(cfg, R, T, s):
+    """adds the stack's per-batch buffers (R = T L rows) to the map s: name -> (shape, dtype name)"""
+    G, GB, H, D, Ho = cfg.G, cfg.GB, cfg.H, cfg.D, cfg.Hout
+    elman = getattr(cfg, "elman", False)
+    if not elman:
+        s["carry"] = ((D, T, H), "f32")
+    for k in range(cfg.rnn_layer):
+        s[f"pre{k}"] = ((R, D, G, H), "f32")
+        if not elman:
+            s[f"gates{k}"] = ((R, D, 4, H), "f32")
+        s[f"hs{k}"] = ((R, Ho), "bf16")
+        s[f"state{k}"] = ((R, Ho), "f32")
+        s[f"dG{k}"] = ((R, D, GB, H), "bf16")
+        if k < cfg.rnn_layer - 1:
+            if cfg.has_dropout:
+                s[f"hd{k}"] = ((R, Ho), "bf16")
+            s[f"dx{k + 1}"] = ((R, Ho), "bf16")
+    return s
+
+
 class RnnMaskStatic:
     """Parameter layout and the bf16 weight arena (independent of the batch)."""
 
     def __init__(self, cfg: RnnMaskConfig):
         self.cfg = cfg
         self.layout = ParamLayout(cfg)
-        G, H, D = cfg.G, cfg.H, cfg.D
-        off = 0
         self.w = {}                # (layer, what) -> element offset in the bf16 arena
-        for k in range(cfg.rnn_layer):
-            kin, kp = cfg.layer_in(k)
-            for what, n in (("ih", D * G * H * kp),          # [D G H][kp]      operand of the input projection
-                            ("ihT", kp * D * 4 * H),         # [kp][D][4][H]    operand of the input gradient (GRU: block 3 stays zero)
-                            ("hh", D * G * H * H),           # [D][G H][H]      forward steps
-                            ("hhT", D * H * G * H)):         # [D][H][G H]      backward steps
-                self.w[(k, what)] = off
-                off += n
+        off = stack_arena(cfg, self.w, 0)
         self.w["fc"] = off;  off += cfg.SF * cfg.Hout        # [S F][Hout]
         self.w["fcT"] = off; off += cfg.Hout * cfg.SFp       # [Hout][SFp]
         self.n_wpack = off
@@ -138,17 +187,7 @@ class RnnMaskStatic:
     def pack_launches(self):
         """[(parameter name, row offset in it, N, K, transpose, ld, arena offset)]: the sehip_rsm_pack_w calls of one step"""
         cfg = self.cfg
-        G, H, D = cfg.G, cfg.H, cfg.D
-        out = []
-        for k in range(cfg.rnn_layer):
-            kin, kp = cfg.layer_in(k)
-            for d, sfx in enumerate(("", "_reverse")[:D]):
-                ih, hh = f"rnn.weight_ih_l{k}{sfx}", f"rnn.weight_hh_l{k}{sfx}"
-                out.append((ih, 0, G * H, kin, 0, kp, self.w[(k, "ih")] + d * G * H * kp))
-                out.append((hh, 0, G * H, H, 0, H, self.w[(k, "hh")] + d * G * H * H))
-                out.append((hh, 0, G * H, H, 1, G * H, self.w[(k, "hhT")] + d * H * G * H))
-                if k > 0:
-                    out.append((ih, 0, G * H, kin, 1, D * 4 * H, self.w[(k, "ihT")] + d * 4 * H))
+        out = stack_pack_launches(cfg, self.w)
         out.append(("fc_layers.0.weight", 0, cfg.SF, cfg.Hout, 0, cfg.Hout, self.w["fc"]))
         out.append(("fc_layers.0.weight", 0, cfg.SF, cfg.Hout, 1, cfg.SFp, self.w["fcT"]))
         return out
@@ -162,23 +201,92 @@ class RnnMaskStatic:
         cfg = self.cfg
         L = B * cfg.audio_channels
         R = T * L
-        G, H, D, Ho = cfg.G, cfg.H, cfg.D, cfg.Hout
+        Ho = cfg.Hout
         s = {"feat": ((R, cfg.Fp), "bf16"), "z": ((R, Ho), "bf16"), "dz": ((R, Ho), "bf16"), "dy": ((R, Ho), "bf16"),
-             "mask": ((R, cfg.SFp), "bf16"), "dpre": ((R, cfg.SFp), "bf16"), "carry": ((D, T, H), "f32"),
+             "mask": ((R, cfg.SFp), "bf16"), "dpre": ((R, cfg.SFp), "bf16"),
              "out": ((B, cfg.num_spk, cfg.audio_channels, cfg.F, T, 2), "f32")}
+        return stack_buffer_shapes(cfg, R, T, s)
+
+
+class RnnStackWorkspace(Workspace):
+    """What the workspaces of rnn-stft-mask and mel-rnn share: guarded allocation and the per-layer loop of the recurrent stack
+    (projection, steps; steps, weight gradients, input gradient), parametrised by the cell.  A subclass sets st, cfg, T, L, R, device,
+    guard, _alloc, bufs, wpack and dropping."""
+
+    def _make(self, name, shape, dtype):
+        n = int(np.prod(shape))
+        g = self.guard
+        if not g:
+            return torch.zeros(shape, dtype=dtype, device=self.device)
+        g = (g + 7) // 8 * 8                      # the payload keeps its 16-byte alignment
+        raw = torch.zeros(n + 2 * g, dtype=dtype, device=self.device)
+        raw[:g] = 7.0
+        raw[g + n:] = 7.0
+        self._alloc[name] = (raw, g, n)
+        return raw[g:g + n].view(shape)
+
+    def guards_intact(self):
+        """names of the buffers whose canary bands were written"""
+        return [k for k, (raw, g, n) in self._alloc.items() if not (bool((raw[:g] == 7.0).all()) and bool((raw[g + n:] == 7.0).all()))]
+
+    def _wp(self, off):
+        return self.wpack.data_ptr() + 2 * off
+
+    def _drop_args(self, model_seed, k, active):
+        thresh, scale = drop_threshold(self.cfg.drop_out) if active else (0, 1.0)
+        return (model_seed & 0xFFFFFFFF, (model_seed >> 32) & 0xFFFFFFFF, ptr(self.ctr_used), k, thresh, scale)
+
+    def stack_forward(self, xin, seed, s):
+        """the layers over xin bf16 [R][Fp]; returns the last layer's output hs bf16 [R][Hout]"""
+        st, cfg, b = self.st, self.cfg, self.bufs
+        R, L, T, H, D, G = self.R, self.L, self.T, cfg.H, cfg.D, cfg.G
+        elman = getattr(cfg, "elman", False)
         for k in range(cfg.rnn_layer):
-            s[f"pre{k}"] = ((R, D, G, H), "f32")
-            s[f"gates{k}"] = ((R, D, 4, H), "f32")
-            s[f"hs{k}"] = ((R, Ho), "bf16")
-            s[f"state{k}"] = ((R, Ho), "f32")
-            s[f"dG{k}"] = ((R, D, 4, H), "bf16")
-            if k < cfg.rnn_layer - 1:
-                s[f"hd{k}"] = ((R, Ho), "bf16")
-                s[f"dx{k + 1}"] = ((R, Ho), "bf16")
-        return s
+            kin, kp = cfg.layer_in(k)
+            call("sehip_rsm_gemm_nt", ptr(xin), kp, self._wp(st.w[(k, "ih")]), kp, R, D * G * H, kp, 0, None, ptr(b[f"pre{k}"]), D * G * H, s)
+            if elman:
+                call("sehip_rsm_elman_fwd", ptr(b[f"pre{k}"]), self._wp(st.w[(k, "hh")]), ptr(b[f"hs{k}"]), ptr(b[f"state{k}"]), T, L, H, D, s)
+                xin = b[f"hs{k}"]
+                continue
+            drop = self.dropping and k < cfg.rnn_layer - 1
+            hd = b[f"hd{k}"] if drop else None
+            call("sehip_rsm_rnn_fwd", int(cfg.gru), ptr(b[f"pre{k}"]), self._wp(st.w[(k, "hh")]), ptr(b[f"gates{k}"]), ptr(b[f"hs{k}"]),
+                 ptr(b[f"state{k}"]), ptr(hd), T, L, H, D, *self._drop_args(seed, k, drop), s)
+            xin = hd if drop else b[f"hs{k}"]
+        return b[f"hs{cfg.rnn_layer - 1}"]
+
+    def stack_backward(self, dh, gp, seed, s):
+        """dh bf16 [R][Hout]: the gradient of the last layer's output; gp(name): address of a parameter's gradient in the flat buffer"""
+        st, cfg, b = self.st, self.cfg, self.bufs
+        R, L, T, H, D, G, GB, Ho = self.R, self.L, self.T, cfg.H, cfg.D, cfg.G, cfg.GB, cfg.Hout
+        elman = getattr(cfg, "elman", False)
+        for k in range(cfg.rnn_layer - 1, -1, -1):
+            kin, kp = cfg.layer_in(k)
+            drop = self.dropping and k < cfg.rnn_layer - 1
+            if elman:
+                call("sehip_rsm_elman_bwd", self._wp(st.w[(k, "hhT")]), ptr(b[f"state{k}"]), ptr(dh), ptr(b[f"dG{k}"]), T, L, H, D, s)
+            else:
+                call("sehip_rsm_rnn_bwd", int(cfg.gru), ptr(b[f"gates{k}"]), self._wp(st.w[(k, "hhT")]), ptr(b[f"state{k}"]), ptr(dh), ptr(b[f"dG{k}"]),
+                     ptr(b["carry"]), T, L, H, D, *self._drop_args(seed, k, drop), s)
+            xin = b["feat"] if k == 0 else (b[f"hd{k - 1}"] if self.dropping else b[f"hs{k - 1}"])
+            dG, hs = b[f"dG{k}"], b[f"hs{k}"]
+            for d, sfx in enumerate(("", "_reverse")[:D]):
+                a0 = dG.data_ptr() + 2 * d * GB * H
+                call("sehip_rsm_gemm_tn", a0, D * GB * H, ptr(xin), kp, R, G * H, kin, 1, 0, gp(f"rnn.weight_ih_l{k}{sfx}"), kin, s)
+                x0 = hs.data_ptr() + 2 * d * H
+                ghh = gp(f"rnn.weight_hh_l{k}{sfx}")
+                shift = 1 if d else -1
+                if cfg.gru:       # r and z: blocks 0, 1; n: block 3 (the gradient of W_hn h carries the factor r)
+                    call("sehip_rsm_gemm_tn", a0, D * 4 * H, x0, Ho, R, 2 * H, H, L, shift, ghh, H, s)
+                    call("sehip_rsm_gemm_tn", a0 + 2 * 3 * H, D * 4 * H, x0, Ho, R, H, H, L, shift, ghh + 4 * 2 * H * H, H, s)
+                else:
+                    call("sehip_rsm_gemm_tn", a0, D * GB * H, x0, Ho, R, G * H, H, L, shift, ghh, H, s)
+            if k > 0:
+                call("sehip_rsm_gemm_nt", ptr(dG), D * GB * H, self._wp(st.w[(k, "ihT")]), D * GB * H, R, kin, D * GB * H, 1, None, ptr(b[f"dx{k}"]), kin, s)
+                dh = b[f"dx{k}"]
 
 
-class RnnMaskWorkspace(Workspace):
+class RnnMaskWorkspace(RnnStackWorkspace):
     """Buffers and launches for inputs [B, C, F, T, 2].  `guard` > 0 (tests): every buffer sits between two bands of that many
     canary elements inside its allocation."""
 
@@ -207,34 +315,11 @@ class RnnMaskWorkspace(Workspace):
         self.x = None
         self.training, self.dropping = True, False
 
-    def _make(self, name, shape, dtype):
-        n = int(np.prod(shape))
-        g = self.guard
-        if not g:
-            return torch.zeros(shape, dtype=dtype, device=self.device)
-        g = (g + 7) // 8 * 8                      # the payload keeps its 16-byte alignment
-        raw = torch.zeros(n + 2 * g, dtype=dtype, device=self.device)
-        raw[:g] = 7.0
-        raw[g + n:] = 7.0
-        self._alloc[name] = (raw, g, n)
-        return raw[g:g + n].view(shape)
-
-    def guards_intact(self):
-        """names of the buffers whose canary bands were written"""
-        return [k for k, (raw, g, n) in self._alloc.items() if not (bool((raw[:g] == 7.0).all()) and bool((raw[g + n:] == 7.0).all()))]
-
-    def _wp(self, off):
-        return self.wpack.data_ptr() + 2 * off
-
-    def _drop_args(self, model_seed, k, active):
-        thresh, scale = drop_threshold(self.cfg.drop_out) if active else (0, 1.0)
-        return (model_seed & 0xFFFFFFFF, (model_seed >> 32) & 0xFFFFFFFF, ptr(self.ctr_used), k, thresh, scale)
-
     def forward(self, x, params, buffers, nbt, seed, counter, training=True):
         """x [B, C, F, T, 2] fp32 on the device -> self.out [B, S, C, F, T, 2]"""
         st, cfg, b = self.st, self.cfg, self.bufs
         Lay = st.layout
-        R, L, T, H, D, G, Ho = self.R, self.L, self.T, cfg.H, cfg.D, cfg.G, cfg.Hout
+        R, L, T, Ho = self.R, self.L, self.T, cfg.Hout
         s = stream()
         self.x, self.training = x, bool(training)
         self.dropping = self.training and cfg.drop_out > 0.0 and cfg.rnn_layer > 1
@@ -243,16 +328,7 @@ class RnnMaskWorkspace(Workspace):
         if self.dropping:
             call("sehip_rsm_counter_next", ptr(counter), ptr(self.ctr_used), s)
         call("sehip_rsm_features", ptr(x), L, cfg.F, T, cfg.Fp, ptr(b["feat"]), s)
-        xin = b["feat"]
-        for k in range(cfg.rnn_layer):
-            kin, kp = cfg.layer_in(k)
-            call("sehip_rsm_gemm_nt", ptr(xin), kp, self._wp(st.w[(k, "ih")]), kp, R, D * G * H, kp, 0, None, ptr(b[f"pre{k}"]), D * G * H, s)
-            drop = self.dropping and k < cfg.rnn_layer - 1
-            hd = b[f"hd{k}"] if drop else None
-            call("sehip_rsm_rnn_fwd", int(cfg.gru), ptr(b[f"pre{k}"]), self._wp(st.w[(k, "hh")]), ptr(b[f"gates{k}"]), ptr(b[f"hs{k}"]),
-                 ptr(b[f"state{k}"]), ptr(hd), T, L, H, D, *self._drop_args(seed, k, drop), s)
-            xin = hd if drop else b[f"hs{k}"]
-        y = b[f"hs{cfg.rnn_layer - 1}"]
+        y = self.stack_forward(b["feat"], seed, s)
         pre = "batchnorm."
         if training:
             call("sehip_wun_bn_stats", ptr(y), R, Ho, ptr(self.part), s)
@@ -270,7 +346,7 @@ class RnnMaskWorkspace(Workspace):
         if not self.training:
             raise SehipError("RNNBaseSTFTMask.backward in eval mode: the backward pass is built for batch statistics only (call model.train())")
         st, cfg, b = self.st, self.cfg, self.bufs
-        R, L, T, H, D, G, Ho = self.R, self.L, self.T, cfg.H, cfg.D, cfg.G, cfg.Hout
+        R, T, Ho = self.R, self.T, cfg.Hout
         s = stream()
         gp = lambda name: grads.data_ptr() + 4 * st.layout.param_off[name][0]
         call("sehip_zero_regions", ptr(grads), grads.numel() * 4, None, 0, None, 0, None, 0, s)
@@ -285,26 +361,5 @@ class RnnMaskWorkspace(Workspace):
         call("sehip_rsm_colsum_finalize", ptr(self.bpart), R, Ho, self._pp(params, "batchnorm.weight"), ptr(self.coef), gp("batchnorm.bias"),
              gp("batchnorm.weight"), ptr(self.bcoef), s)
         call("sehip_rsm_bn_bwd_apply", ptr(b["dz"]), ptr(y), ptr(self.coef), ptr(self.bcoef), R, Ho, ptr(b["dy"]), s)
-        dh = b["dy"]
-        for k in range(cfg.rnn_layer - 1, -1, -1):
-            kin, kp = cfg.layer_in(k)
-            drop = self.dropping and k < cfg.rnn_layer - 1
-            call("sehip_rsm_rnn_bwd", int(cfg.gru), ptr(b[f"gates{k}"]), self._wp(st.w[(k, "hhT")]), ptr(b[f"state{k}"]), ptr(dh), ptr(b[f"dG{k}"]),
-                 ptr(b["carry"]), T, L, H, D, *self._drop_args(seed, k, drop), s)
-            xin = b["feat"] if k == 0 else (b[f"hd{k - 1}"] if self.dropping else b[f"hs{k - 1}"])
-            dG, hs = b[f"dG{k}"], b[f"hs{k}"]
-            for d, sfx in enumerate(("", "_reverse")[:D]):
-                a0 = dG.data_ptr() + 2 * d * 4 * H
-                call("sehip_rsm_gemm_tn", a0, D * 4 * H, ptr(xin), kp, R, G * H, kin, 1, 0, gp(f"rnn.weight_ih_l{k}{sfx}"), kin, s)
-                x0 = hs.data_ptr() + 2 * d * H
-                ghh = gp(f"rnn.weight_hh_l{k}{sfx}")
-                shift = 1 if d else -1
-                if cfg.gru:       # r and z: blocks 0, 1; n: block 3 (the gradient of W_hn h carries the factor r)
-                    call("sehip_rsm_gemm_tn", a0, D * 4 * H, x0, Ho, R, 2 * H, H, L, shift, ghh, H, s)
-                    call("sehip_rsm_gemm_tn", a0 + 2 * 3 * H, D * 4 * H, x0, Ho, R, H, H, L, shift, ghh + 4 * 2 * H * H, H, s)
-                else:
-                    call("sehip_rsm_gemm_tn", a0, D * 4 * H, x0, Ho, R, 4 * H, H, L, shift, ghh, H, s)
-            if k > 0:
-                call("sehip_rsm_gemm_nt", ptr(dG), D * 4 * H, self._wp(st.w[(k, "ihT")]), D * 4 * H, R, kin, D * 4 * H, 1, None, ptr(b[f"dx{k}"]), kin, s)
-                dh = b[f"dx{k}"]
+        self.stack_backward(b["dy"], gp, seed, s)
         return grads
