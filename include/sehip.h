@@ -835,6 +835,41 @@ int sehip_ha_compressor_fwd(const float* z, long rows, long n, int W, double thr
                             double attenuation, int soft_clip, double* ws, float* gain, float* out, void* stream);
 int sehip_ha_compressor_bwd(const float* dout, const float* out, const float* gain, long count, int soft_clip, float* dz, void* stream);
 
+/* ---- U-Net on the power spectrogram (src/model/unet.py:9-146, `unet`; csrc/unet.hip).  Activations are channels-last bf16
+ *      [R][T_l][F_l][C] (T frames, F rows per frame, both halved by floor per level), C a power of two >= 8, at most 2^32 elements per
+ *      tensor (the dropout index is 32 bits wide); spec / out / dout are fp32 [R][uc][F][T][2].  Cp = uc rounded up to a multiple of 8:
+ *      the padding channels of every Cp-wide tensor are exact zeros.  No atomics: every sum goes through one row of partials per
+ *      workgroup in a fixed order.  Dropout arguments as sehip_rsm_rnn_fwd's (thresh = 0: none); the keep decision is recomputed from the
+ *      element's index in the FULL-RESOLUTION tensor, in forward and backward.
+ *      features      : amp bf16 [R][T][F][Cp] = re^2 + im^2 of spec
+ *      mask_fwd      : out = spec * LeakyReLU_0.01(scale y + shift), y bf16 [R][T][F][Cp] the head's pre-BatchNorm output
+ *      mask_bwd      : dm bf16 [R][T][F][Cp] = dout_re spec_re + dout_im spec_im
+ *      bn_finalize   : sehip_wun_bn_finalize over the partial rows of sehip_wun_bn_stats(y, rows, C) for a tensor whose channels
+ *                      Cr .. C-1 are padding: their records are zero and gamma / beta / running statistics hold Cr entries
+ *      bn_act        : z = drop(LeakyReLU_0.01(scale y + shift)), y and z bf16 [rows][C]
+ *      bn_act_pool   : the same followed by MaxPool2d(2): zp bf16 [R][T/2][F/2][C] and code, one 16-bit word per 8 channels
+ *                      [R][T/2][F/2][C/8], 2 bits per channel = 2 (F offset) + (T offset) of the maximum, ties to the first in the order
+ *                      (0,0), (F+0,T+1), (F+1,T+0), (F+1,T+1).  An odd last frame / row belongs to no window
+ *      bn_bwd_reduce : per channel sum g and sum g xhat into part (sehip_wun_bn_scratch_floats(R T F, C) floats; then
+ *                      sehip_wun_bn_bwd_finalize), g = LeakyReLU'(scale y + shift) drop'(incoming).  code == NULL: incoming = dz bf16
+ *                      [R][T][F][C]; else dz is the pooled gradient [R][T/2][F/2][C]: the coded element of each window takes it, the
+ *                      other three and an odd last frame / row exact zero
+ *      bn_bwd_apply  : dy = gamma rstd (g - mean(g) - xhat mean(g xhat)) with the same g */
+int sehip_unet_features(const float* spec, int R, int uc, int F, int T, int Cp, void* amp, void* stream);
+int sehip_unet_mask_fwd(const void* y, const float* coef, const float* spec, int R, int uc, int F, int T, int Cp, float* out, void* stream);
+int sehip_unet_mask_bwd(const float* dout, const float* spec, int R, int uc, int F, int T, int Cp, void* dm, void* stream);
+int sehip_unet_bn_finalize(const float* part, const void* y, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                           long* num_batches_tracked, long rows, int C, int Cr, float eps, float momentum, int training, float* coef,
+                           void* stream);
+int sehip_unet_bn_act(const void* y, const float* coef, long rows, int C, unsigned seed_lo, unsigned seed_hi, const void* ctr, int layer,
+                      unsigned thresh, float scale, void* z, void* stream);
+int sehip_unet_bn_act_pool(const void* y, const float* coef, int R, int T, int F, int C, unsigned seed_lo, unsigned seed_hi, const void* ctr,
+                           int layer, unsigned thresh, float scale, void* zp, void* code, void* stream);
+int sehip_unet_bn_bwd_reduce(const void* dz, const void* code, const void* y, const float* coef, int R, int T, int F, int C, unsigned seed_lo,
+                             unsigned seed_hi, const void* ctr, int layer, unsigned thresh, float scale, float* part, void* stream);
+int sehip_unet_bn_bwd_apply(const void* dz, const void* code, const void* y, const float* coef, const float* bcoef, int R, int T, int F, int C,
+                            unsigned seed_lo, unsigned seed_hi, const void* ctr, int layer, unsigned thresh, float scale, void* dy, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,30 +20,13 @@
 // ceil(rows / 16))), a head of Linear + ReLU + Linear + Sigmoid (two more epilogues of rsm_gemm_nt_kernel) and a mask backward that
 // carries the sigmoid's derivative.
 #include "common.h"
+#include "drop.h"
 
 namespace {
 
 __device__ __forceinline__ float rsm_sigm(float x) { return 1.f / (1.f + __expf(-x)); }
 
-// ---- dropout: counter-based, bits = mix(mix(index ^ key) + golden), key from (seed, step counter, layer) ---------------------------
-struct RsmDrop {
-    unsigned seed_lo, seed_hi;
-    const unsigned* ctr;      // the step counter this forward pass took (device memory; never read on the host)
-    int layer;
-    unsigned thresh;          // round(p 2^24); an element is kept when its top 24 bits are >= thresh; 0 = no dropout here
-    float scale;              // 1 / (1 - p), 0 for p = 1
-};
-__device__ __forceinline__ unsigned rsm_mix(unsigned x) {
-    x ^= x >> 16; x *= 0x85ebca6bu; x ^= x >> 13; x *= 0xc2b2ae35u; x ^= x >> 16;
-    return x;
-}
-__device__ __forceinline__ unsigned rsm_key(const RsmDrop& d) {
-    return rsm_mix(d.seed_lo ^ rsm_mix(d.seed_hi ^ rsm_mix(d.ctr[0] * 0x9e3779b9u + (unsigned)d.layer)));
-}
-__device__ __forceinline__ bool rsm_keep(unsigned key, unsigned idx, unsigned thresh) {
-    return (rsm_mix(rsm_mix(idx ^ key) + 0x9e3779b9u) >> 8) >= thresh;
-}
-
+// ---- dropout: counter-based (RsmDrop, rsm_mix / rsm_key / rsm_keep: csrc/drop.h, shared with csrc/unet.hip) ------------------------------
 __global__ void rsm_counter_next_kernel(unsigned long long* ctr, unsigned* used) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
         const unsigned long long c = ctr[0];

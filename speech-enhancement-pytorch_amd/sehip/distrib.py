@@ -18,11 +18,12 @@ from .model.demucs import Demucs
 from .model.wav_unet import WavUnet
 from .model.rnn_stft_mask import RNNBaseSTFTMask
 from .model.mel_rnn import MelRNN
+from .model.unet import UNet
 from .optim import FlatOptimizer
 from .utils import obj2dict
 
 MODEL_REGISTRY = {"dccrn": DCCRN, "dcunet": DCUnet, "dnn": DeepNeuralNetwork, "conv-tasnet": ConvTasNet, "demucs": Demucs,
-                  "wav-unet": WavUnet, "rnn-stft-mask": RNNBaseSTFTMask, "mel-rnn": MelRNN}
+                  "wav-unet": WavUnet, "rnn-stft-mask": RNNBaseSTFTMask, "mel-rnn": MelRNN, "unet": UNet}
 _REFERENCE_NAMES = ("dnn", "mel-rnn", "unet", "dccrn", "dcunet", "demucs", "wav-unet", "conv-tasnet", "crn", "rnn-stft-mask")
 
 
