@@ -3,8 +3,8 @@
 // network output and the incoming gradient stay fp32 [R][uc][F][T][2].
 //   features     amp = re^2 + im^2 as bf16 [R][T][F][Cp] (Cp = uc rounded up to 8, padding channels exact zeros): the (F, T)
 //                transposition through an LDS tile
-//   bn_finalize  sehip_wun_bn_finalize for a tensor whose last C - Cr channels are padding: their records are zero (z = 0, dy = 0)
-//                and no parameter / running statistic beyond Cr is touched
+//   bn_finalize  sehip_wun_bn_finalize (the same kernel, csrc/clbn.h) for a tensor whose last C - Cr channels are padding: their
+//                records are zero (z = 0, dy = 0) and no parameter / running statistic beyond Cr is touched
 //   bn_act       z = drop(LeakyReLU_0.01(scale y + shift)) at full resolution
 //   bn_act_pool  the same followed by MaxPool2d(2) in one pass: the activated full-resolution tensor is never stored.  Writes the
 //                pooled z and a 2-bit argmax code per output (8 channels = one 16-bit word): code = 2 (F offset) + (T offset), ties to
@@ -15,40 +15,21 @@
 //   mask_fwd     out = spec * LeakyReLU_0.01(BN(y_head)), transposed back to [F][T]
 //   mask_bwd     dm = dout_re spec_re + dout_im spec_im as bf16 [R][T][F][Cp]
 // The streaming kernels have csrc/wavunet.hip's form: thread t of a 256-thread workgroup owns the 16-byte piece t % (C / 8) of row
-// t / (C / 8) of the workgroup's rows, its channels' coefficients stay in registers.  Sums: wun_block_partials' fixed order, one row
+// t / (C / 8) of the workgroup's rows, its channels' coefficients stay in registers.  Sums: clbn_block_partials' fixed order (csrc/clbn.h), one row
 // of partials per workgroup, added by sehip_wun_bn_bwd_finalize.  No atomics.  Dropout: csrc/drop.h, the keep decision is recomputed
 // from the element's index in the full-resolution tensor, forward and backward.
 #include <stdlib.h>
 #include "common.h"
 #include "rbn.h"
+#include "clbn.h"
 #include "drop.h"
 
 #define UNET_SLOPE 0.01f
 #define UNET_TILE 32
 
-extern "C" long sehip_wun_bn_scratch_floats(long rows, int C);
-
 namespace {
 
 __device__ __forceinline__ float unet_lrelu(float v) { return v > 0.f ? v : UNET_SLOPE * v; }
-
-// the workgroup's rows added in row order (csrc/wavunet.hip: wun_block_partials)
-template <int NS>
-__device__ __forceinline__ void unet_block_partials(const float (&s)[NS][8], int nq, int rpb, int C, float* __restrict__ out, float* lds) {
-#pragma unroll
-    for (int k = 0; k < NS; ++k) {
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < 8; ++j) lds[threadIdx.x * 8 + j] = s[k][j];
-        __syncthreads();
-        for (int c = threadIdx.x; c < C; c += 256) {
-            const int q = c >> 3, j = c & 7;
-            float a = 0.f;
-            for (int rl = 0; rl < rpb; ++rl) a += lds[(rl * nq + q) * 8 + j];
-            out[(size_t)k * C + c] = a;
-        }
-    }
-}
 
 // ---- spectrum -> channels-last bf16 ----------------------------------------------------------------------------------------------------
 // MODE 0: re^2 + im^2 of spec; MODE 1: dout_re spec_re + dout_im spec_im.  grid (T tiles, F tiles, R * Cp / 8): one group of 8 channels
@@ -124,42 +105,6 @@ __global__ __launch_bounds__(256) void unet_mask_fwd_kernel(const bf16_raw* __re
                 out[o] = make_float2(z.x * m, z.y * m);
             }
         }
-}
-
-// ---- BatchNorm records with padding channels ----------------------------------------------------------------------------------------
-__device__ __forceinline__ double unet_wave_total(const float* __restrict__ part, int nblk, size_t stride, size_t off) {
-    double a = 0.0;
-    for (int b = threadIdx.x & 63; b < nblk; b += 64) a += (double)part[(size_t)b * stride + off];
-    return wave_sum_d(a);
-}
-
-__global__ void unet_bn_finalize_kernel(const float* __restrict__ part, int nblk, const bf16_raw* __restrict__ y, const float* __restrict__ gamma,
-                                        const float* __restrict__ beta, float* __restrict__ rm, float* __restrict__ rv, long* __restrict__ nbt,
-                                        long rows, int C, int Cr, float eps, float momentum, int training, float4* __restrict__ coef) {
-    const int c = blockIdx.x;
-    if (c >= Cr) {
-        if (threadIdx.x == 0) coef[c] = make_float4(0.f, 0.f, 0.f, 0.f);
-        return;
-    }
-    double mean, var;
-    if (training) {
-        const double a0 = unet_wave_total(part, nblk, (size_t)2 * C, c);
-        const double a1 = unet_wave_total(part, nblk, (size_t)2 * C, (size_t)C + c);
-        if (threadIdx.x != 0) return;
-        const double n = (double)rows, md = a0 / n;
-        var = a1 / n - md * md;
-        if (var < 0.0) var = 0.0;
-        mean = (double)bf2f(y[c]) + md;
-        rm[c] = (float)((1.0 - (double)momentum) * (double)rm[c] + (double)momentum * mean);
-        rv[c] = (float)((1.0 - (double)momentum) * (double)rv[c] + (double)momentum * (var * n / (n - 1.0)));
-        if (c == 0 && nbt) nbt[0] += 1;
-    } else {
-        if (threadIdx.x != 0) return;
-        mean = (double)rm[c]; var = (double)rv[c];
-    }
-    const double rstd = 1.0 / sqrt(var + (double)eps);
-    const double sc = (double)gamma[c] * rstd;
-    coef[c] = make_float4((float)sc, (float)((double)beta[c] - mean * sc), (float)mean, (float)rstd);
 }
 
 // ---- forward ------------------------------------------------------------------------------------------------------------------------
@@ -286,7 +231,7 @@ __global__ __launch_bounds__(256) void unet_bn_bwd_reduce_kernel(const bf16_raw*
             s[1][j] += gg * (a.v[j] - k[j].z) * k[j].w;
         }
     }
-    unet_block_partials<2>(s, nq, rpb, C, part + (size_t)blockIdx.x * 2 * C, lds);
+    clbn_block_partials<2>(s, nq, rpb, C, part + (size_t)blockIdx.x * 2 * C, lds);
 }
 
 // pass 2: dy = gamma rstd (g - mean(g) - xh mean(g xh))
@@ -322,14 +267,6 @@ RsmDrop unet_make_drop(unsigned seed_lo, unsigned seed_hi, const void* ctr, int 
     RsmDrop d;
     d.seed_lo = seed_lo; d.seed_hi = seed_hi; d.ctr = (const unsigned*)ctr; d.layer = layer; d.thresh = thresh; d.scale = scale;
     return d;
-}
-
-int unet_blocks(long rows, int C, int per, int cap) {
-    const long rpb = 256 / (C >> 3);
-    long g = (rows + rpb * per - 1) / (rpb * per);
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
 }
 
 }  // namespace
@@ -389,8 +326,8 @@ extern "C" int sehip_unet_bn_finalize(const float* part, const void* y, const fl
     SEHIP_REQUIRE(Cr >= 1 && Cr <= C, "unet_bn_finalize: Cr=%d must be in [1, C=%d]", Cr, C);
     SEHIP_REQUIRE(gamma && beta && running_mean && running_var && coef, "unet_bn_finalize: null pointer");
     SEHIP_REQUIRE(!training || (part && y && rows > 1), "unet_bn_finalize: training needs the partial sums, y and more than one row");
-    const int nblk = (int)(sehip_wun_bn_scratch_floats(rows, C) / (2L * C));      // the rows sehip_wun_bn_stats wrote
-    unet_bn_finalize_kernel<<<C, 64, 0, (hipStream_t)stream>>>(part, nblk, (const bf16_raw*)y, gamma, beta, running_mean, running_var,
+    const int nblk = clbn_sum_blocks(rows, C);      // the rows sehip_wun_bn_stats wrote
+    clbn_bn_finalize_kernel<<<C, 64, 0, (hipStream_t)stream>>>(part, nblk, (const bf16_raw*)y, gamma, beta, running_mean, running_var,
                                                              num_batches_tracked, rows, C, Cr, eps, momentum, training, (float4*)coef);
     SEHIP_CHECK_LAUNCH("unet_bn_finalize");
     return 0;
@@ -401,7 +338,7 @@ extern "C" int sehip_unet_bn_act(const void* y, const float* coef, long rows, in
     if (int e = check_unet("unet_bn_act", rows, 1, 1, C)) return e;
     if (int e = check_drop("unet_bn_act", ctr, thresh)) return e;
     SEHIP_REQUIRE(y && coef && z, "unet_bn_act: null pointer");
-    unet_bn_act_kernel<<<unet_blocks(rows, C, 4, 4096), 256, 0, (hipStream_t)stream>>>(
+    unet_bn_act_kernel<<<clbn_blocks(rows, C, 4, 4096), 256, 0, (hipStream_t)stream>>>(
         (const bf16_raw*)y, (const float4*)coef, (unsigned)rows, C, unet_make_drop(seed_lo, seed_hi, ctr, layer, thresh, scale), (bf16_raw*)z);
     SEHIP_CHECK_LAUNCH("unet_bn_act");
     return 0;
@@ -414,7 +351,7 @@ extern "C" int sehip_unet_bn_act_pool(const void* y, const float* coef, int R, i
     SEHIP_REQUIRE(T >= 2 && F >= 2, "unet_bn_act_pool: T=%d and F=%d must be at least 2 (one pooling window)", T, F);
     SEHIP_REQUIRE(y && coef && zp && code, "unet_bn_act_pool: null pointer");
     const long rows2 = (long)R * (T / 2) * (F / 2);
-    unet_bn_act_pool_kernel<<<unet_blocks(rows2, C, 2, 4096), 256, 0, (hipStream_t)stream>>>(
+    unet_bn_act_pool_kernel<<<clbn_blocks(rows2, C, 2, 4096), 256, 0, (hipStream_t)stream>>>(
         (const bf16_raw*)y, (const float4*)coef, (unsigned)rows2, T, F, C, unet_make_drop(seed_lo, seed_hi, ctr, layer, thresh, scale),
         (bf16_raw*)zp, (unsigned short*)code);
     SEHIP_CHECK_LAUNCH("unet_bn_act_pool");
@@ -431,7 +368,7 @@ extern "C" int sehip_unet_bn_bwd_reduce(const void* dz, const void* code, const 
     SEHIP_REQUIRE(!code || (T >= 2 && F >= 2), "unet_bn_bwd_reduce: the pooled form needs T=%d and F=%d of at least 2", T, F);
     SEHIP_REQUIRE(dz && y && coef && part, "unet_bn_bwd_reduce: null pointer");
     const long rows = (long)R * T * F;
-    const int nblk = (int)(sehip_wun_bn_scratch_floats(rows, C) / (2L * C));
+    const int nblk = clbn_sum_blocks(rows, C);
     unet_bn_bwd_reduce_kernel<<<nblk, 256, 0, (hipStream_t)stream>>>((const bf16_raw*)dz, (const unsigned short*)code, (const bf16_raw*)y,
                                                                    (const float4*)coef, (unsigned)rows, T, F, C,
                                                                    unet_make_drop(seed_lo, seed_hi, ctr, layer, thresh, scale), part);
@@ -447,7 +384,7 @@ extern "C" int sehip_unet_bn_bwd_apply(const void* dz, const void* code, const v
     SEHIP_REQUIRE(!code || (T >= 2 && F >= 2), "unet_bn_bwd_apply: the pooled form needs T=%d and F=%d of at least 2", T, F);
     SEHIP_REQUIRE(dz && y && coef && bcoef && dy, "unet_bn_bwd_apply: null pointer");
     const long rows = (long)R * T * F;
-    unet_bn_bwd_apply_kernel<<<unet_blocks(rows, C, 4, 4096), 256, 0, (hipStream_t)stream>>>(
+    unet_bn_bwd_apply_kernel<<<clbn_blocks(rows, C, 4, 4096), 256, 0, (hipStream_t)stream>>>(
         (const bf16_raw*)dz, (const unsigned short*)code, (const bf16_raw*)y, (const float4*)coef, (const float4*)bcoef, (unsigned)rows, T, F, C,
         unet_make_drop(seed_lo, seed_hi, ctr, layer, thresh, scale), (bf16_raw*)dy);
     SEHIP_CHECK_LAUNCH("unet_bn_bwd_apply");

@@ -9,48 +9,15 @@
 // All of them stream 16-byte pieces (8 bf16 channels per lane): thread t of a 256-thread workgroup owns piece t % (C/8) of row
 // t / (C/8) of the workgroup's rows, so a wave reads consecutive addresses and a thread's channels (its coefficients) are fixed.
 // Sums: in-thread, then over the workgroup's rows in row order through LDS, one row of partials per workgroup, added by a
-// finalize launch (one wave per output: lane-strided in double + the fixed shuffle tree).  No atomics: run-to-run identical.
+// finalize launch (one wave per output: lane-strided in double + the fixed shuffle tree): csrc/clbn.h, shared with csrc/unet.hip.
+// No atomics: run-to-run identical.
 #include <stdlib.h>
 #include "common.h"
 #include "rbn.h"
+#include "clbn.h"
 
 #define WUN_SLOPE 0.1f
-#define WUN_MAX_BLOCKS 512
 #define WUN_TAPS 15
-
-static inline int wun_rpb(int C) { return 256 / (C >> 3); }
-static inline int wun_blocks(long rows, int C, int per, int cap) {
-    long g = (rows + (long)wun_rpb(C) * per - 1) / ((long)wun_rpb(C) * per);
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-static inline int wun_sum_blocks(long rows, int C) { return wun_blocks(rows, C, 8, WUN_MAX_BLOCKS); }
-
-// the workgroup's rows added in row order: out[k * C + c], k < NS.  lds: 256 * 8 floats
-template <int NS>
-__device__ __forceinline__ void wun_block_partials(const float (&s)[NS][8], int nq, int rpb, int C, float* __restrict__ out, float* lds) {
-#pragma unroll
-    for (int k = 0; k < NS; ++k) {
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < 8; ++j) lds[threadIdx.x * 8 + j] = s[k][j];
-        __syncthreads();
-        for (int c = threadIdx.x; c < C; c += 256) {
-            const int q = c >> 3, j = c & 7;
-            float a = 0.f;
-            for (int rl = 0; rl < rpb; ++rl) a += lds[(rl * nq + q) * 8 + j];
-            out[(size_t)k * C + c] = a;
-        }
-    }
-}
-
-// one wave: sum over the workgroups' rows of part[b * stride + off]
-__device__ __forceinline__ double wun_wave_total(const float* __restrict__ part, int nblk, size_t stride, size_t off) {
-    double a = 0.0;
-    for (int b = threadIdx.x & 63; b < nblk; b += 64) a += (double)part[(size_t)b * stride + off];
-    return wave_sum_d(a);
-}
 
 __device__ __forceinline__ float wun_lrelu(float v) { return v > 0.f ? v : WUN_SLOPE * v; }
 
@@ -112,13 +79,13 @@ __global__ __launch_bounds__(256) void wun_enc0_wgrad_kernel(const bf16_raw* __r
             for (int j = 0; j < 8; ++j) s[WUN_TAPS][j] += g.v[j];
         }
     const size_t blk = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
-    wun_block_partials<WUN_TAPS + 1>(s, nq, rpb, C, part + blk * (WUN_TAPS + 1) * C, lds);
+    clbn_block_partials<WUN_TAPS + 1>(s, nq, rpb, C, part + blk * (WUN_TAPS + 1) * C, lds);
 }
 
 // one wave per (k, c): dW[c][k] (k < 15), db[c] (k = 15)
 __global__ void wun_enc0_wgrad_finalize_kernel(const float* __restrict__ part, int nblk, int C, float* __restrict__ dW, float* __restrict__ db) {
     const int k = blockIdx.x / C, c = blockIdx.x - k * C;
-    const double a = wun_wave_total(part, nblk, (size_t)(WUN_TAPS + 1) * C, (size_t)k * C + c);
+    const double a = clbn_wave_total(part, nblk, (size_t)(WUN_TAPS + 1) * C, (size_t)k * C + c);
     if (threadIdx.x != 0) return;
     if (k < WUN_TAPS) dW[c * WUN_TAPS + k] = (float)a;
     else db[c] = (float)a;
@@ -147,33 +114,7 @@ __global__ __launch_bounds__(256) void wun_bn_stats_kernel(const bf16_raw* __res
             }
         }
     }
-    wun_block_partials<2>(s, nq, rpb, C, part + (size_t)blockIdx.x * 2 * C, lds);
-}
-
-// coef record per channel: scale (gamma rstd), shift (beta - mean scale), mean, rstd.  One wave per channel.
-__global__ void wun_bn_finalize_kernel(const float* __restrict__ part, int nblk, const bf16_raw* __restrict__ y, const float* __restrict__ gamma,
-                                       const float* __restrict__ beta, float* __restrict__ rm, float* __restrict__ rv, long* __restrict__ nbt,
-                                       long rows, int C, float eps, float momentum, int training, float4* __restrict__ coef) {
-    const int c = blockIdx.x;
-    double mean, var;
-    if (training) {
-        const double a0 = wun_wave_total(part, nblk, (size_t)2 * C, c);
-        const double a1 = wun_wave_total(part, nblk, (size_t)2 * C, (size_t)C + c);
-        if (threadIdx.x != 0) return;
-        const double n = (double)rows, md = a0 / n;
-        var = a1 / n - md * md;
-        if (var < 0.0) var = 0.0;
-        mean = (double)bf2f(y[c]) + md;
-        rm[c] = (float)((1.0 - (double)momentum) * (double)rm[c] + (double)momentum * mean);
-        rv[c] = (float)((1.0 - (double)momentum) * (double)rv[c] + (double)momentum * (var * n / (n - 1.0)));   // nn.BatchNorm1d: UNBIASED
-        if (c == 0 && nbt) nbt[0] += 1;
-    } else {
-        if (threadIdx.x != 0) return;
-        mean = (double)rm[c]; var = (double)rv[c];
-    }
-    const double rstd = 1.0 / sqrt(var + (double)eps);
-    const double sc = (double)gamma[c] * rstd;
-    coef[c] = make_float4((float)sc, (float)((double)beta[c] - mean * sc), (float)mean, (float)rstd);
+    clbn_block_partials<2>(s, nq, rpb, C, part + (size_t)blockIdx.x * 2 * C, lds);
 }
 
 __global__ __launch_bounds__(256) void wun_bn_apply_kernel(const bf16_raw* __restrict__ y, const float4* __restrict__ coef, long rows, int C,
@@ -307,15 +248,15 @@ __global__ __launch_bounds__(256) void wun_bn_bwd_reduce_kernel(const bf16_raw* 
             }
         }
     }
-    wun_block_partials<2>(s, nq, rpb, C, part + (size_t)blockIdx.x * 2 * C, lds);
+    clbn_block_partials<2>(s, nq, rpb, C, part + (size_t)blockIdx.x * 2 * C, lds);
 }
 
 // bcoef record per channel: gamma rstd, mean(g), mean(g xh)
 __global__ void wun_bn_bwd_finalize_kernel(const float* __restrict__ part, int nblk, const float4* __restrict__ coef, long rows, int C,
                                            float* __restrict__ dgamma, float* __restrict__ dbeta, float4* __restrict__ bcoef) {
     const int c = blockIdx.x;
-    const double a0 = wun_wave_total(part, nblk, (size_t)2 * C, c);
-    const double a1 = wun_wave_total(part, nblk, (size_t)2 * C, (size_t)C + c);
+    const double a0 = clbn_wave_total(part, nblk, (size_t)2 * C, c);
+    const double a1 = clbn_wave_total(part, nblk, (size_t)2 * C, (size_t)C + c);
     if (threadIdx.x != 0) return;
     dbeta[c] = (float)a0;
     dgamma[c] = (float)a1;
@@ -394,14 +335,14 @@ __global__ __launch_bounds__(256) void wun_out_bwd_kernel(const float* __restric
             if (q == 0) { s[1][0] += dp * x[r]; s[1][1] += dp; }
         }
     }
-    wun_block_partials<2>(s, nq, rpb, C, part + (size_t)blockIdx.x * 2 * C, lds);
+    clbn_block_partials<2>(s, nq, rpb, C, part + (size_t)blockIdx.x * 2 * C, lds);
 }
 
 // one wave per output: dW[0 .. C) | dW[C] (the waveform's weight) | db
 __global__ void wun_out_bwd_finalize_kernel(const float* __restrict__ part, int nblk, int C, float* __restrict__ dW, float* __restrict__ db) {
     const int c = blockIdx.x;
     const size_t off = c < C ? (size_t)c : (size_t)C + (c - C);
-    const double a = wun_wave_total(part, nblk, (size_t)2 * C, off);
+    const double a = clbn_wave_total(part, nblk, (size_t)2 * C, off);
     if (threadIdx.x != 0) return;
     if (c <= C) dW[c] = (float)a;
     else db[0] = (float)a;
@@ -421,9 +362,9 @@ static int check_bt(const char* who, int B, int T) {
 
 extern "C" long sehip_wun_bn_scratch_floats(long rows, int C) {
     if (C < 8 || C > 2048 || C % 8 || rows < 1) return 0;
-    return (long)wun_sum_blocks(rows, C) * 2L * C;
+    return (long)clbn_sum_blocks(rows, C) * 2L * C;
 }
-static inline int wun_enc0_wg_blocks(int T, int C) { return wun_blocks(T, C, 16, 16); }
+static inline int wun_enc0_wg_blocks(int T, int C) { return clbn_blocks(T, C, 16, 16); }
 extern "C" long sehip_wun_enc0_wgrad_scratch_floats(int B, int T, int C0) {
     if (C0 < 8 || C0 > 2048 || C0 % 8 || B < 1 || T < 1) return 0;
     return (long)B * wun_enc0_wg_blocks(T, C0) * (WUN_TAPS + 1L) * C0;
@@ -434,7 +375,7 @@ extern "C" int sehip_wun_enc0_fwd(const float* x, const float* W, const float* b
     if (int e = check_wun("wun_enc0_fwd", (long)B * T, C0)) return e;
     if (int e = check_bt("wun_enc0_fwd", B, T)) return e;
     SEHIP_REQUIRE(x && W && bias && y0, "wun_enc0_fwd: null pointer");
-    wun_enc0_fwd_kernel<<<dim3(wun_blocks(T, C0, 4, 2048), B), 256, 0, (hipStream_t)stream>>>(x, W, bias, T, C0, (bf16_raw*)y0);
+    wun_enc0_fwd_kernel<<<dim3(clbn_blocks(T, C0, 4, 2048), B), 256, 0, (hipStream_t)stream>>>(x, W, bias, T, C0, (bf16_raw*)y0);
     SEHIP_CHECK_LAUNCH("wun_enc0_fwd");
     return 0;
 }
@@ -455,7 +396,7 @@ extern "C" int sehip_wun_bn_stats(const void* y, long rows, int C, float* part, 
     if (int e = check_wun("wun_bn_stats", rows, C)) return e;
     SEHIP_REQUIRE(rows > 1, "wun_bn_stats: BatchNorm needs more than one value per channel (rows=%ld)", rows);
     SEHIP_REQUIRE(y && part, "wun_bn_stats: null pointer");
-    wun_bn_stats_kernel<<<wun_sum_blocks(rows, C), 256, 0, (hipStream_t)stream>>>((const bf16_raw*)y, rows, C, part);
+    wun_bn_stats_kernel<<<clbn_sum_blocks(rows, C), 256, 0, (hipStream_t)stream>>>((const bf16_raw*)y, rows, C, part);
     SEHIP_CHECK_LAUNCH("wun_bn_stats");
     return 0;
 }
@@ -466,8 +407,8 @@ extern "C" int sehip_wun_bn_finalize(const float* part, const void* y, const flo
     if (int e = check_wun("wun_bn_finalize", rows, C)) return e;
     SEHIP_REQUIRE(gamma && beta && running_mean && running_var && coef, "wun_bn_finalize: null pointer");
     SEHIP_REQUIRE(!training || (part && y && rows > 1), "wun_bn_finalize: training needs the partial sums, y and more than one row");
-    wun_bn_finalize_kernel<<<C, 64, 0, (hipStream_t)stream>>>(part, wun_sum_blocks(rows, C), (const bf16_raw*)y, gamma, beta, running_mean,
-                                                            running_var, num_batches_tracked, rows, C, eps, momentum, training, (float4*)coef);
+    clbn_bn_finalize_kernel<<<C, 64, 0, (hipStream_t)stream>>>(part, clbn_sum_blocks(rows, C), (const bf16_raw*)y, gamma, beta, running_mean,
+                                                             running_var, num_batches_tracked, rows, C, C, eps, momentum, training, (float4*)coef);
     SEHIP_CHECK_LAUNCH("wun_bn_finalize");
     return 0;
 }
@@ -475,7 +416,7 @@ extern "C" int sehip_wun_bn_finalize(const float* part, const void* y, const flo
 extern "C" int sehip_wun_bn_apply(const void* y, const float* coef, long rows, int C, void* z, void* stream) {
     if (int e = check_wun("wun_bn_apply", rows, C)) return e;
     SEHIP_REQUIRE(y && coef && z, "wun_bn_apply: null pointer");
-    wun_bn_apply_kernel<<<wun_blocks(rows, C, 4, 4096), 256, 0, (hipStream_t)stream>>>((const bf16_raw*)y, (const float4*)coef, rows, C, (bf16_raw*)z);
+    wun_bn_apply_kernel<<<clbn_blocks(rows, C, 4, 4096), 256, 0, (hipStream_t)stream>>>((const bf16_raw*)y, (const float4*)coef, rows, C, (bf16_raw*)z);
     SEHIP_CHECK_LAUNCH("wun_bn_apply");
     return 0;
 }
@@ -485,7 +426,7 @@ extern "C" int sehip_wun_bn_apply_up2(const void* y, const float* coef, int B, i
     if (int e = check_bt("wun_bn_apply_up2", B, Tin)) return e;
     SEHIP_REQUIRE(Tin >= 2, "wun_bn_apply_up2: the interpolation needs at least two source frames (Tin=%d)", Tin);
     SEHIP_REQUIRE(y && coef && up, "wun_bn_apply_up2: null pointer");
-    wun_bn_apply_up2_kernel<<<dim3(wun_blocks(2L * Tin, C, 4, 2048), B), 256, 0, (hipStream_t)stream>>>((const bf16_raw*)y, (const float4*)coef, Tin,
+    wun_bn_apply_up2_kernel<<<dim3(clbn_blocks(2L * Tin, C, 4, 2048), B), 256, 0, (hipStream_t)stream>>>((const bf16_raw*)y, (const float4*)coef, Tin,
                                                                                                       C, (bf16_raw*)up);
     SEHIP_CHECK_LAUNCH("wun_bn_apply_up2");
     return 0;
@@ -496,7 +437,7 @@ extern "C" int sehip_wun_up2_bwd(const void* dup, int B, int Tin, int C, void* d
     if (int e = check_bt("wun_up2_bwd", B, Tin)) return e;
     SEHIP_REQUIRE(Tin >= 2, "wun_up2_bwd: the interpolation needs at least two source frames (Tin=%d)", Tin);
     SEHIP_REQUIRE(dup && dz, "wun_up2_bwd: null pointer");
-    wun_up2_bwd_kernel<<<dim3(wun_blocks(Tin, C, 4, 2048), B), 256, 0, (hipStream_t)stream>>>((const bf16_raw*)dup, Tin, C, (bf16_raw*)dz);
+    wun_up2_bwd_kernel<<<dim3(clbn_blocks(Tin, C, 4, 2048), B), 256, 0, (hipStream_t)stream>>>((const bf16_raw*)dup, Tin, C, (bf16_raw*)dz);
     SEHIP_CHECK_LAUNCH("wun_up2_bwd");
     return 0;
 }
@@ -506,7 +447,7 @@ extern "C" int sehip_wun_bn_bwd_reduce(const void* dz_full, const void* dz_even,
     if (int e = check_wun("wun_bn_bwd_reduce", rows, C)) return e;
     SEHIP_REQUIRE(dz_full && y && coef && part, "wun_bn_bwd_reduce: null pointer");
     SEHIP_REQUIRE(!dz_even || rows % 2 == 0, "wun_bn_bwd_reduce: dz_even needs an even number of frames per utterance (rows=%ld)", rows);
-    wun_bn_bwd_reduce_kernel<<<wun_sum_blocks(rows, C), 256, 0, (hipStream_t)stream>>>((const bf16_raw*)dz_full, (const bf16_raw*)dz_even,
+    wun_bn_bwd_reduce_kernel<<<clbn_sum_blocks(rows, C), 256, 0, (hipStream_t)stream>>>((const bf16_raw*)dz_full, (const bf16_raw*)dz_even,
                                                                                      (const bf16_raw*)y, (const float4*)coef, rows, C, part);
     SEHIP_CHECK_LAUNCH("wun_bn_bwd_reduce");
     return 0;
@@ -516,7 +457,7 @@ extern "C" int sehip_wun_bn_bwd_finalize(const float* part, const float* coef, l
                                          void* stream) {
     if (int e = check_wun("wun_bn_bwd_finalize", rows, C)) return e;
     SEHIP_REQUIRE(part && coef && dgamma && dbeta && bcoef, "wun_bn_bwd_finalize: null pointer");
-    wun_bn_bwd_finalize_kernel<<<C, 64, 0, (hipStream_t)stream>>>(part, wun_sum_blocks(rows, C), (const float4*)coef, rows, C, dgamma, dbeta,
+    wun_bn_bwd_finalize_kernel<<<C, 64, 0, (hipStream_t)stream>>>(part, clbn_sum_blocks(rows, C), (const float4*)coef, rows, C, dgamma, dbeta,
                                                                 (float4*)bcoef);
     SEHIP_CHECK_LAUNCH("wun_bn_bwd_finalize");
     return 0;
@@ -527,7 +468,7 @@ extern "C" int sehip_wun_bn_bwd_apply(const void* dz_full, const void* dz_even, 
     if (int e = check_wun("wun_bn_bwd_apply", rows, C)) return e;
     SEHIP_REQUIRE(dz_full && y && coef && bcoef && dy, "wun_bn_bwd_apply: null pointer");
     SEHIP_REQUIRE(!dz_even || rows % 2 == 0, "wun_bn_bwd_apply: dz_even needs an even number of frames per utterance (rows=%ld)", rows);
-    wun_bn_bwd_apply_kernel<<<wun_blocks(rows, C, 4, 4096), 256, 0, (hipStream_t)stream>>>(
+    wun_bn_bwd_apply_kernel<<<clbn_blocks(rows, C, 4, 4096), 256, 0, (hipStream_t)stream>>>(
         (const bf16_raw*)dz_full, (const bf16_raw*)dz_even, (const bf16_raw*)y, (const float4*)coef, (const float4*)bcoef, rows, C, (bf16_raw*)dy);
     SEHIP_CHECK_LAUNCH("wun_bn_bwd_apply");
     return 0;
@@ -547,7 +488,7 @@ extern "C" int sehip_wun_out_bwd(const float* dout, const float* out, const void
                                  float* dW, float* db, float* scratch, void* stream) {
     if (int e = check_wun("wun_out_bwd", rows, C0)) return e;
     SEHIP_REQUIRE(dout && out && z && x && W && dz && dW && db && scratch, "wun_out_bwd: null pointer");
-    const int nblk = wun_sum_blocks(rows, C0);
+    const int nblk = clbn_sum_blocks(rows, C0);
     wun_out_bwd_kernel<<<nblk, 256, 0, (hipStream_t)stream>>>(dout, out, (const bf16_raw*)z, x, W, rows, C0, (bf16_raw*)dz, scratch);
     SEHIP_CHECK_LAUNCH("wun_out_bwd");
     wun_out_bwd_finalize_kernel<<<C0 + 2, 64, 0, (hipStream_t)stream>>>(scratch, nblk, C0, dW, db);

@@ -16,18 +16,20 @@ Every convolution is a product of the implicit-GEMM engine (csrc/gemm.hip, gener
     descriptors (dOut = the scattered destination).  The far-end pad frame / row of an `up` buffer is zero from allocation and never
     written; its bias goes through the descriptor, the four classes' bias sums land in one region;
   * weight gradients: the same descriptors with dOut as the second operand, on the side stream.
-Everything else is csrc/unet.hip (+ sehip_wun_bn_stats / sehip_wun_bn_bwd_finalize of csrc/wavunet.hip).  The full-resolution output
+Everything else is csrc/unet.hip (+ sehip_wun_bn_stats / sehip_wun_bn_bwd_finalize of csrc/wavunet.hip; the sums of both files are
+csrc/clbn.h).  The full-resolution output
 of an encoder block has one reader, MaxPool2d(2): sehip_unet_bn_act_pool applies BatchNorm, LeakyReLU, dropout and the pool in one pass
 and never stores it.
+
+The product graph itself (Prod, the arenas, the un-pack table, the bound descriptors with their canary bands, prologue and un-pack) is
+sehip/prodgraph.py, shared with plan_wavunet.py; this module holds the network's own products, its shape refusals and its launch sequence.
 """
 import numpy as np
 import torch
 
-from . import _lib
 from ._lib import call, ptr, stream, SehipError
-from .plan import Arena, CGemmDesc, ParamLayout, bind_chunk_table, dense_ntab, enc_entry, npad_of, pad_ktab, BF16
 from .plan_rnnmask import drop_threshold
-from .workspace import Buf, GemmWorkspace
+from .prodgraph import ProdDeviceTables, ProdStatic, ProdWorkspace
 
 BN_EPS, BN_MOMENTUM, WIDTH0 = 1e-5, 0.1, 16
 MAX_LAYERS = 4
@@ -92,35 +94,6 @@ class UNetConfig:
         return out
 
 
-class Prod:
-    """One product of the engine (independent of R, T, F).  rows: [(source, frame offset, row offset, channel offset)] per 8-channel chunk
-    of K; widx [N][8 len(rows)]: parameter index of every weight, -1 = zero; srcs: buffer names; dsts: [(buffer, columns)]; level: the
-    row space is T_level x F_level per item; stride: (tmul, fmul) of the sources; scatter: (toff, fadd) with tmul = fmul = 2 in the
-    destination (a parity class of a transposed convolution) or None; res: buffer added to what goes to dsts[0]; dout: the buffer a
-    forward product's weight-gradient twin reads as dOut; bias_key: products that share one bias-gradient region."""
-
-    def __init__(self, name, rows, widx, srcs, dsts, level, bias=None, kind="fwd", dout=None, stride=(1, 1), scatter=None, res=None,
-                 bias_key=None):
-        self.name, self.srcs, self.dsts, self.level, self.kind, self.dout = name, srcs, dsts, level, kind, dout
-        self.stride, self.scatter, self.res, self.bias_key = stride, scatter, res, bias_key
-        self.ktab, self.K = pad_ktab(list(rows))
-        n, k0 = widx.shape
-        assert k0 == 8 * len(rows)
-        self.N, self.Npad = n, npad_of(n)
-        w = np.full((self.Npad, self.K), -1, dtype=np.int32)
-        w[:n, :k0] = enc_entry(widx, 0)
-        self.wtab = w.reshape(-1)
-        self.bias = None
-        if bias is not None:
-            b = np.full((self.Npad, 2), -1, dtype=np.int32)
-            b[:n, 0] = enc_entry(np.asarray(bias), 0)
-            self.bias = b
-        assert sum(c for _, c in dsts) == n
-        nt = np.concatenate([dense_ntab(c, c, q, 0) for q, (_, c) in enumerate(dsts)])
-        self.ntab = np.concatenate([nt, np.zeros((self.Npad // 4 - nt.shape[0], 4), dtype=np.int32)])
-        self.w_off = self.b_off = self.dw_off = self.db_off = self.kt_off = self.nt_off = None
-
-
 def conv3_tables(w, srcs, co_s):
     """forward product of a 3x3 convolution, weight index array w [co][sum of real source channels][kF][kT]; srcs [(real, stored
     channels)] in concatenation order -> (chunk rows, widx [co_s][9 sum stored])"""
@@ -156,30 +129,15 @@ def conv3_dgrad_tables(w, srcs, ndst, co_s):
     return rows, np.concatenate(cols, 1)
 
 
-class UNetStatic:
-    """Products, packed-weight layout and gradient un-packing table (independent of R, T, F)."""
+class UNetStatic(ProdStatic):
+    """Products, packed-weight layout and gradient un-packing table (independent of R, T, F).  A product's sources are buffer names."""
+    plan_name = "UNet"
 
     def __init__(self, cfg: UNetConfig):
-        self.cfg = cfg
-        self.layout = Lay = ParamLayout(cfg)
-        ia = Lay.index_array
+        super().__init__(cfg)
+        ia = self.layout.index_array
         L, w, uc, Cp = cfg.L, cfg.width, cfg.uc, cfg.Cp
-        self.prods = {}
-        self.buffers = {}       # name -> (level, stored channels)
-        self.norms = {}         # key -> dict(pre, C stored, Cr real, level, y, goff)
-        ga = Arena(16)
-
-        def buf(name, level, c):
-            assert name not in self.buffers
-            self.buffers[name] = (level, c)
-
-        def prod(*a, **k):
-            p = Prod(*a, **k)
-            assert p.name not in self.prods
-            self.prods[p.name] = p
-
-        def norm(key, pre, c, cr, level, y):
-            self.norms[key] = dict(pre=pre, C=c, Cr=cr, level=level, y=y, goff=ga.reserve(2 * c))
+        buf, prod, norm = self.buf, self.prod, self.norm
 
         def double_conv(key, pre, srcs, mid, out, level, dg=None, res=None):
             """srcs [(buffer, real, stored)]; mid / out (real, stored); dg: [buffer names] the first convolution's input gradient goes
@@ -198,8 +156,8 @@ class UNetStatic:
             prod(key + ".c2", rows, widx, [key + ".z1"], [(key + ".y2", os_)], level, dout=key + ".dy2")
             rows, widx = conv3_dgrad_tables(w2, [(mr, ms)], 1, os_)
             prod(key + ".c2.dg", rows, widx, [key + ".dy2"], [(key + ".dz1", ms)], level, kind="dgrad")
-            norm(key + ".n1", pre + "1.", ms, mr, level, key + ".y1")
-            norm(key + ".n2", pre + "4.", os_, orl, level, key + ".y2")
+            norm(key + ".n1", pre + "1.", ms, level, key + ".y1", cr=mr)
+            norm(key + ".n2", pre + "4.", os_, level, key + ".y2", cr=orl)
 
         def up(key, pre, src, dsrc, cin, level):
             """ConvTranspose2d(cin -> cin / 2, k = 2, s = 2) from `src` (level + 1) into key.up (level); d key.up -> dsrc"""
@@ -243,86 +201,17 @@ class UNetStatic:
         # (amp takes no gradient: the mixture is data)
         double_conv("o", "outconv.conv.double_conv.", [("o.up", w[0] // 2, w[0] // 2), ("amp", uc, Cp)], (uc, Cp), (uc, Cp), 0, dg=["o.dup"])
 
-        wa, ba, kta, nta = Arena(64), Arena(4), Arena(1), Arena(1)
-        shared_db = {}
-        for p in self.prods.values():
-            p.kt_off = kta.add(p.ktab)
-            p.nt_off = nta.add(p.ntab)
-            p.w_off = wa.add(p.wtab)
-            if p.bias is not None:
-                p.b_off = ba.add(p.bias)
-            if p.kind == "fwd":
-                p.dw_off = ga.reserve(p.Npad * p.K)
-                if p.bias is not None:
-                    if p.bias_key not in shared_db:
-                        shared_db[p.bias_key] = ga.reserve(p.Npad)
-                    p.db_off = shared_db[p.bias_key]
-        self.n_wpack, self.n_bpack, self.n_gpack = wa.size, max(ba.size, 4), ga.size
-        if max(self.n_wpack, self.n_gpack, Lay.n_params) >= 2 ** 30:
-            raise SehipError("sehip UNet: the 32-bit packing tables hold fewer than 2^30 entries")
-        self.wtab = wa.build(np.int32)
-        self.btab = ba.build(np.int32, 2) if ba.size else np.full((4, 2), -1, dtype=np.int32)
-        self.ktab = kta.build(np.int32, 4)
-        self.ntab = nta.build(np.int32, 4, fill=0)
-        for p in self.prods.values():
-            p.wtab = None            # the arena's table holds the only copy from here on
-        wa.pieces = []
-        self.utab1 = self._build_unpack_table()
-
-    def _build_unpack_table(self):
-        """int32 [n_params]: (index in the packed-gradient buffer) << 1 of every parameter element, -1 for the layout's padding."""
-        Lay = self.layout
-        ia = Lay.index_array
-        tab = np.full(Lay.n_params, -1, dtype=np.int32)
-        total = [0]
-
-        def put(pidx, gidx):
-            pidx = np.asarray(pidx, dtype=np.int64).reshape(-1)
-            gidx = np.asarray(gidx, dtype=np.int64).reshape(-1)
-            assert (tab[pidx] < 0).all()
-            tab[pidx] = (gidx << 1).astype(np.int32)
-            total[0] += pidx.size
-
-        done_bias = set()
-        for p in self.prods.values():
-            if p.dw_off is None:
-                continue
-            w = self.wtab[p.w_off:p.w_off + p.Npad * p.K]
-            m = np.flatnonzero(w >= 0)
-            put(w[m] >> 1, p.dw_off + m)
-            if p.db_off is not None and p.db_off not in done_bias:      # the four parity classes of one transposed convolution share it
-                done_bias.add(p.db_off)
-                b = p.bias[:, 0]
-                m = np.flatnonzero(b >= 0)
-                put(b[m] >> 1, p.db_off + m)
-        for nm in self.norms.values():
-            put(ia(nm["pre"] + "weight"), nm["goff"] + np.arange(nm["Cr"]))
-            put(ia(nm["pre"] + "bias"), nm["goff"] + nm["C"] + np.arange(nm["Cr"]))
-        used = np.zeros(Lay.n_params, dtype=bool)
-        for name in Lay.param_names:
-            off, shape = Lay.param_off[name]
-            used[off:off + (int(np.prod(shape)) if len(shape) else 1)] = True
-        assert total[0] == int(used.sum()) and (tab[used] >= 0).all() and (tab[~used] < 0).all(), \
-            "every UNet parameter has exactly one packed-gradient entry"
-        return tab
+        self._assemble()
 
 
-class UNetDeviceTables:
-    def __init__(self, st: UNetStatic, device):
-        f = lambda a: torch.from_numpy(a).to(device)
-        self.wtab, self.btab, self.ntab, self.utab1 = f(st.wtab), f(st.btab), f(st.ntab), f(st.utab1)
-        self.tensor_offsets = f(st.layout.tensor_offsets)
-        self.wpack = torch.zeros(st.n_wpack, dtype=BF16, device=device)
-        self.bpack = torch.zeros(st.n_bpack, dtype=torch.float32, device=device)
+UNetDeviceTables = ProdDeviceTables
 
 
-class UNetWorkspace(GemmWorkspace):
+class UNetWorkspace(ProdWorkspace):
     """Buffers and bound descriptors for inputs [R, uc, F, T, 2].  `guard` > 0 (tests): every activation buffer sits between two bands
     of that many canary elements inside its allocation."""
-    GUARD_BF16 = -1234.0
 
     def __init__(self, st: UNetStatic, tables: UNetDeviceTables, R, F, T, device, guard=0):
-        super().__init__()
         cfg = st.cfg
         L = cfg.L
         if F < 2 ** L or T < 2 ** L:
@@ -335,102 +224,13 @@ class UNetWorkspace(GemmWorkspace):
                              "dropout index and the row counters are 32 bits wide)")
         if T >= 2 ** 15 or F >= 2 ** 15:
             raise SehipError(f"UNet: F={F}, T={T} must be below 32768 (16-bit offsets of the engine's chunk table)")
-        self.st, self.tb, self.R, self.F, self.T, self.device = st, tables, R, F, T, device
-        self.Tl = [T >> l for l in range(L + 1)]
-        self.Fl = [F >> l for l in range(L + 1)]
-        self.guard, self._alloc = int(guard), {}
-        self.bufs = {}
-        for name, (level, c) in st.buffers.items():
-            t = self._make(name, (R, self.Tl[level], self.Fl[level], c), BF16)
-            self.bufs[name] = Buf(t, self.Tl[level], self.Fl[level], c)
+        self.R, self.F, self.T = R, F, T
+        super().__init__(st, tables, R, [T >> l for l in range(L + 1)], [F >> l for l in range(L + 1)], device, guard=guard)
         self.code = {l: self._make(f"code{l}", (R, self.Tl[l + 1], self.Fl[l + 1], cfg.width[l] // 8), torch.int16) for l in range(L)}
         self.out = torch.zeros(R, cfg.uc, F, T, 2, dtype=torch.float32, device=device)
-        lib = _lib.lib()
-        self.coef, self.bcoef, self.part, self.bpart = {}, {}, {}, {}
-        for k, nm in st.norms.items():
-            rows = R * self.Tl[nm["level"]] * self.Fl[nm["level"]]
-            self.coef[k] = torch.zeros(nm["C"], 4, dtype=torch.float32, device=device)
-            self.bcoef[k] = torch.zeros(nm["C"], 4, dtype=torch.float32, device=device)
-            # one row of partial sums per workgroup; every layer its own (the op-local tests read them back)
-            self.part[k] = torch.zeros(max(int(lib.sehip_wun_bn_scratch_floats(rows, nm["C"])), 1), dtype=torch.float32, device=device)
-            self.bpart[k] = torch.zeros_like(self.part[k])
-        self.gpack = torch.zeros(st.n_gpack, dtype=torch.float32, device=device)
         self.ctr_used = torch.zeros(2, dtype=torch.int32, device=device)
         self.spec = None
         self.training, self.dropping, self.seed = True, False, 0
-        self._bwd_clean = False
-        self.side = self._new_side_stream(device) if device.type == "cuda" else None
-        self._bind()
-
-    def _make(self, name, shape, dtype):
-        n = int(np.prod(shape))
-        g = self.guard
-        if not g:
-            t = torch.zeros(shape, dtype=dtype, device=self.device)
-        else:
-            whole = torch.full((n + 2 * g,), self.GUARD_BF16 if dtype == BF16 else -21846, dtype=dtype, device=self.device)
-            self._alloc[name] = whole
-            t = whole[g:g + n].view(shape)
-            t.zero_()
-        return t
-
-    def guards_intact(self):
-        """names of the buffers whose canary bands were written (tests)"""
-        g, bad = self.guard, []
-        for name, whole in self._alloc.items():
-            want = self.GUARD_BF16 if whole.dtype == BF16 else -21846
-            if not (bool((whole[:g] == want).all()) and bool((whole[-g:] == want).all())):
-                bad.append(name)
-        return bad
-
-    def _bind(self):
-        st, tb, R = self.st, self.tb, self.R
-        self.desc = {}
-        kt = st.ktab.copy()
-        for p in st.prods.values():
-            bind_chunk_table(st.ktab, kt, p.kt_off, p.K // 8, [(self.bufs[s].F, self.bufs[s].C) for s in p.srcs])
-        self.ktab_dev = torch.from_numpy(kt).to(self.device)
-        for name, p in st.prods.items():
-            d = CGemmDesc()
-            tt, jj = self.Tl[p.level], self.Fl[p.level]
-            for q, s in enumerate(p.srcs):
-                b = self.bufs[s]
-                if p.stride == (1, 1):
-                    assert (b.Tst, b.F) == (tt, jj), (name, s)
-                else:
-                    assert b.Tst >= 2 * tt and b.F >= 2 * jj, (name, s)
-                d.src[q].ptr, d.src[q].T, d.src[q].F, d.src[q].C, d.src[q].tlo, d.src[q].thi = b.ptr, b.Tst, b.F, b.C, 0, b.Tst
-            for q, (bname, cols) in enumerate(p.dsts):
-                ob = self.bufs[bname]
-                assert ob.C == cols, (name, bname)
-                d.dst[q].ptr, d.dst[q].T, d.dst[q].F, d.dst[q].C, d.dst[q].is_f32 = ob.ptr, ob.Tst, ob.F, ob.C, 0
-                if p.scatter is None:
-                    assert (ob.Tst, ob.F) == (tt, jj), (name, bname)
-                    d.dst[q].toff, d.dst[q].fmul, d.dst[q].fadd, d.dst[q].tmul = 0, 1, 0, 1
-                else:
-                    assert ob.Tst >= 2 * tt and ob.F >= 2 * jj, (name, bname)
-                    d.dst[q].toff, d.dst[q].fmul, d.dst[q].fadd, d.dst[q].tmul = p.scatter[0], 2, p.scatter[1], 2
-            d.ktab = self.ktab_dev.data_ptr() + 16 * p.kt_off
-            d.ntab = tb.ntab.data_ptr() + 16 * p.nt_off
-            d.W = tb.wpack.data_ptr() + 2 * p.w_off
-            if p.b_off is not None:
-                d.bias = tb.bpack.data_ptr() + 4 * p.b_off
-            d.M, d.N, d.Npad, d.K = R * tt * jj, p.N, p.Npad, p.K
-            d.TT, d.J, d.tmul, d.fmul = tt, jj, p.stride[0], p.stride[1]
-            if p.res is not None:
-                rb, ob = self.bufs[p.res], self.bufs[p.dsts[0][0]]
-                assert (rb.Tst, rb.F, rb.C) == (ob.Tst, ob.F, ob.C), (name, p.res)
-                d.res = rb.ptr
-            self.desc[name] = d
-            if p.dw_off is not None:
-                w = CGemmDesc.from_buffer_copy(d)
-                w.dW = self.gpack.data_ptr() + 4 * p.dw_off
-                if p.db_off is not None:
-                    w.dbias = self.gpack.data_ptr() + 4 * p.db_off
-                gb, ob = self.bufs[p.dout], self.bufs[p.dsts[0][0]]
-                assert (gb.Tst, gb.F, gb.C) == (ob.Tst, ob.F, ob.C), (name, p.dout)
-                w.dst[0].ptr = gb.ptr
-                self.desc[name + ".wg"] = w
 
     # ---- launches (gemm, wgrad: GemmWorkspace) ------------------------------------------------------------------------
     def _drop(self, site):
@@ -440,14 +240,10 @@ class UNetWorkspace(GemmWorkspace):
         thresh, scale = drop_threshold(self.st.cfg.p)
         return (self.seed & 0xFFFFFFFF, (self.seed >> 32) & 0xFFFFFFFF, ptr(self.ctr_used), site, thresh, scale)
 
-    def _rows(self, key):
-        lv = self.st.norms[key]["level"]
-        return self.R * self.Tl[lv] * self.Fl[lv]
-
     def _norm_coef(self, key, params, buffers, nbt):
         """batch (training) or running (eval) statistics of a layer -> its coefficient records"""
         nm, Lay = self.st.norms[key], self.st.layout
-        y, pre, rows = self.bufs[nm["y"]], nm["pre"], self._rows(key)
+        y, pre, rows = self.bufs[nm["y"]], nm["pre"], self._norm_rows(key)
         if self.training:
             call("sehip_wun_bn_stats", y.ptr, rows, nm["C"], ptr(self.part[key]), stream())
         call("sehip_unet_bn_finalize", ptr(self.part[key]), y.ptr, self._pp(params, pre + "weight"), self._pp(params, pre + "bias"),
@@ -457,7 +253,7 @@ class UNetWorkspace(GemmWorkspace):
 
     def _act(self, key, z, site=None):
         nm = self.st.norms[key]
-        call("sehip_unet_bn_act", self.bufs[nm["y"]].ptr, ptr(self.coef[key]), self._rows(key), nm["C"], *self._drop(site), self.bufs[z].ptr,
+        call("sehip_unet_bn_act", self.bufs[nm["y"]].ptr, ptr(self.coef[key]), self._norm_rows(key), nm["C"], *self._drop(site), self.bufs[z].ptr,
              stream())
 
     def _double_conv(self, key, params, buffers, nbt):
@@ -475,15 +271,12 @@ class UNetWorkspace(GemmWorkspace):
 
     def forward(self, spec, params, buffers, nbt, seed=0, counter=None, training=True):
         """spec [R, uc, F, T, 2] fp32 on the device -> self.out, same shape."""
-        st, cfg, b, tb = self.st, self.st.cfg, self.bufs, self.tb
+        cfg, b = self.st.cfg, self.bufs
         R, F, T, L = self.R, self.F, self.T, cfg.L
         s = stream()
         self.spec, self.training, self.seed = spec, bool(training), int(seed)
         self.dropping = self.training and cfg.p > 0.0
-        call("sehip_zero_regions", ptr(self.gpack), self.gpack.numel() * 4, None, 0, None, 0, None, 0, s)
-        self._bwd_clean = True
-        call("sehip_pack_bf16", ptr(params), ptr(tb.wtab), st.n_wpack, ptr(tb.wpack), s)
-        call("sehip_pack_f32", ptr(params), ptr(tb.btab), st.n_bpack, ptr(tb.bpack), s)
+        self._prologue(params)
         if self.dropping:
             if counter is None:
                 raise SehipError("UNet.forward: dropout needs the model's step counter")
@@ -516,7 +309,7 @@ class UNetWorkspace(GemmWorkspace):
         cp = ptr(code) if code is not None else None
         drop = self._drop(site)
         call("sehip_unet_bn_bwd_reduce", self.bufs[dz].ptr, cp, y.ptr, ptr(self.coef[key]), *geo, *drop, ptr(self.bpart[key]), stream())
-        call("sehip_wun_bn_bwd_finalize", ptr(self.bpart[key]), ptr(self.coef[key]), self._rows(key), nm["C"], g, g + 4 * nm["C"],
+        call("sehip_wun_bn_bwd_finalize", ptr(self.bpart[key]), ptr(self.coef[key]), self._norm_rows(key), nm["C"], g, g + 4 * nm["C"],
              ptr(self.bcoef[key]), stream())
         call("sehip_unet_bn_bwd_apply", self.bufs[dz].ptr, cp, y.ptr, ptr(self.coef[key]), ptr(self.bcoef[key]), *geo, *drop, self.bufs[dy].ptr,
              stream())
@@ -542,12 +335,9 @@ class UNetWorkspace(GemmWorkspace):
         """dout [R, uc, F, T, 2] fp32 -> flat parameter gradients (overwritten)."""
         if not self.training:
             raise SehipError("UNet.backward in eval mode: the backward pass is built for batch statistics only (call model.train())")
-        st, cfg, b, tb = self.st, self.st.cfg, self.bufs, self.tb
+        cfg, b = self.st.cfg, self.bufs
         R, F, T, L = self.R, self.F, self.T, cfg.L
-        if not self._bwd_clean:            # a second backward pass over the same forward
-            self.gpack.zero_()
-        self._bwd_clean = False
-        self._chain_dirty = True
+        self._begin_backward()
         call("sehip_unet_mask_bwd", ptr(dout), ptr(self.spec), R, cfg.uc, F, T, cfg.Cp, b["o.dz2"].ptr, stream())
         self._double_conv_bwd("o", "o.dz2")
         self._up_bwd("o")
@@ -559,11 +349,4 @@ class UNetWorkspace(GemmWorkspace):
         self._double_conv_bwd("m", "m.dz2", site=DROP_MIDDLE)
         for l in range(L - 1, -1, -1):
             self._double_conv_bwd(f"e{l}", f"dp{l}", code=self.code[l], site=DROP_ENCODER if l == L - 1 else None)
-        self.join_side()
-        np_ = st.layout.n_params
-        if tail is not None:      # FlatOptimizer's accumulators: the un-pack also takes the clipping norm / metric sums
-            call("sehip_unpack_grad1_sums", ptr(self.gpack), ptr(tb.utab1), np_, ptr(grads), tail[2], tail[3], tail[0], tail[1], tail[4],
-                 None, stream())
-        else:
-            call("sehip_unpack_grad1", ptr(self.gpack), ptr(tb.utab1), np_, ptr(grads), stream())
-        return grads
+        return self._unpack(grads, tail)

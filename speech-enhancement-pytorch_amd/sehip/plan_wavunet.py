@@ -13,16 +13,16 @@ kernels, bias / bias gradient through the descriptor):
 Everything else is csrc/wavunet.hip: the first layer straight from the fp32 waveform, BatchNorm1d + LeakyReLU(0.1) (batch statistics
 forward / backward), the same fused with the align-corners x2 linear upsampling (the activated tensor of a decoder / middle layer is
 never stored), the upsampling's adjoint as a gather, and the ``cat + 1x1 + tanh`` head.
-"""
-import os
 
+The product graph itself (Prod, the arenas, the un-pack table, the bound descriptors, prologue and un-pack) is sehip/prodgraph.py, shared
+with plan_unet.py; this module holds the network's own products, its shape refusals and its launch sequence.
+"""
 import numpy as np
 import torch
 
 from . import _lib
 from ._lib import call, ptr, stream, SehipError
-from .plan import Arena, CGemmDesc, ParamLayout, bind_chunk_table, dense_ntab, npad_of, pad_ktab, BF16
-from .workspace import Buf, GemmWorkspace
+from .prodgraph import ProdDeviceTables, ProdStatic, ProdWorkspace
 
 BN_EPS, BN_MOMENTUM, ENC_TAPS, DEC_TAPS = 1e-5, 0.1, 15, 5
 
@@ -83,60 +83,21 @@ class WavUnetConfig:
         return out
 
 
-class Prod:
-    """One product of the engine (batch- and length-independent part).  srcs: [(buffer, pair view?)]; dsts: [(buffer, columns)];
-    rows: [(source, frame offset, channel offset)] one per 8-channel chunk of K; level: the row space is T_level frames per item."""
-
-    def __init__(self, name, rows, widx, srcs, dsts, level, bias=None, kind="fwd", dout=None):
-        self.name, self.srcs, self.dsts, self.level, self.kind, self.dout = name, srcs, dsts, level, kind, dout
-        self.ktab, self.K = pad_ktab([(s, fo, 0, co) for s, fo, co in rows])
-        n, k0 = widx.shape
-        self.N, self.Npad = n, npad_of(n)
-        w = np.full((self.Npad, self.K), -1, dtype=np.int32)
-        w[:n, :k0] = (widx.astype(np.int64) << 1).astype(np.int32)
-        self.wtab = w.reshape(-1)
-        self.bias = None
-        if bias is not None:
-            b = np.full((self.Npad, 2), -1, dtype=np.int32)
-            b[:n, 0] = (np.asarray(bias, dtype=np.int64) << 1).astype(np.int32)
-            self.bias = b
-        assert sum(c for _, c in dsts) == n
-        nt = np.concatenate([dense_ntab(c, c, q, 0) for q, (_, c) in enumerate(dsts)])
-        self.ntab = np.concatenate([nt, np.zeros((self.Npad // 4 - nt.shape[0], 4), dtype=np.int32)])
-        self.w_off = self.b_off = self.dw_off = self.db_off = self.kt_off = self.nt_off = None
-
-
 def _chunks(src, frame_off, cn):
     assert cn % 8 == 0
-    return [(src, frame_off, 8 * q) for q in range(cn // 8)]
+    return [(src, frame_off, 0, 8 * q) for q in range(cn // 8)]
 
 
-class WavUnetStatic:
-    """Products, packed-weight layout and gradient un-packing table (independent of batch and clip length)."""
+class WavUnetStatic(ProdStatic):
+    """Products, packed-weight layout and gradient un-packing table (independent of batch and clip length).  A product's sources are
+    (buffer, pair view?) tuples (WavUnetWorkspace._src_view)."""
+    plan_name = "WavUnet"
 
     def __init__(self, cfg: WavUnetConfig):
-        self.cfg = cfg
-        self.layout = L = ParamLayout(cfg)
-        # SEHIP_WUN_KEEP_GRADS=1 (tests): every layer keeps its own gradient buffers so that every kernel can be checked op-locally after
-        # one step.  The plan gives every layer its own buffers anyway (nothing is shared yet): the switch is recorded and changes nothing, one plan serves both.
-        self.keep_grads = bool(os.environ.get("SEHIP_WUN_KEEP_GRADS"))
-        ia = L.index_array
+        super().__init__(cfg)
+        ia = self.layout.index_array
         n, ci = cfg.n, cfg.ci
-        self.prods = {}
-        self.buffers = {}       # name -> (level, channels)
-        self.norms = {}         # layer key -> dict(pre=parameter prefix, C, level, y, goff)
-        ga = Arena(16)
-
-        def buf(name, level, c):
-            self.buffers[name] = (level, c)
-
-        def prod(*a, **k):
-            p = Prod(*a, **k)
-            assert p.name not in self.prods
-            self.prods[p.name] = p
-
-        def norm(key, pre, c, level, y):
-            self.norms[key] = dict(pre=pre, C=c, level=level, y=y, goff=ga.reserve(2 * c))
+        ga, buf, prod, norm = self.ga, self.buf, self.prod, self.norm
 
         def conv15(key, pre, zin, cin, cout, level, y, dy, dzeven):
             """15 taps over the pair view of zin (level - 1) -> y; input gradient -> dzeven [T_level][cin]"""
@@ -154,11 +115,11 @@ class WavUnetStatic:
             buf(k + ".y", l, cout); buf(k + ".z", l, cout); buf(k + ".dy", l, cout); buf(k + ".dskip", l, cout); buf(k + ".dzeven", l + 1, cout)
             if l > 0:
                 conv15(k, f"encoder.{l}.main.", f"e{l - 1}.z", cin, cout, l, k + ".y", k + ".dy", f"e{l - 1}.dzeven")
-            norm(k, f"encoder.{l}.main.", cout, l, k + ".y")
+            norm(k, f"encoder.{l}.main.1.", cout, l, k + ".y")
         cm = n * ci
         buf("m.y", n, cm); buf("m.dy", n, cm); buf("m.dz", n, cm)
         conv15("m", "middle.", f"e{n - 1}.z", cm, cm, n, "m.y", "m.dy", f"e{n - 1}.dzeven")
-        norm("m", "middle.", cm, n, "m.y")
+        norm("m", "middle.1.", cm, n, "m.y")
         for i in range(n):
             cu, cs, co = cfg.dec_channels(i)
             lv = n - 1 - i
@@ -172,80 +133,18 @@ class WavUnetStatic:
             rows = [r for p in range(DEC_TAPS) for r in _chunks(0, DEC_TAPS // 2 - p, co)]
             prod(k + ".dg", rows, w.transpose(1, 2, 0).reshape(cu + cs, DEC_TAPS * co), [(k + ".dy", False)],
                  [(k + ".dup", cu), (f"e{lv}.dskip", cs)], lv, kind="dgrad")
-            norm(k, pre, co, lv, k + ".y")
+            norm(k, pre + "1.", co, lv, k + ".y")
         buf("zl", 0, ci)                                               # the last decoder layer's activated output: the head reads it
         self.out_goff = ga.reserve(ci + 2)                              # dW [C0 + 1] | db
 
-        wa, ba, kta, nta = Arena(64), Arena(4), Arena(1), Arena(1)
-        for p in self.prods.values():
-            p.kt_off = kta.add(p.ktab)
-            p.nt_off = nta.add(p.ntab)
-            p.w_off = wa.add(p.wtab)
-            if p.bias is not None:
-                p.b_off = ba.add(p.bias)
-            if p.kind == "fwd":
-                p.dw_off = ga.reserve(p.Npad * p.K)
-                p.db_off = ga.reserve(p.Npad)
-        self.n_wpack, self.n_bpack, self.n_gpack = wa.size, max(ba.size, 4), ga.size
-        if max(self.n_wpack, self.n_gpack, L.n_params) >= 2 ** 30:
-            raise SehipError("sehip WavUnet: the 32-bit packing tables hold fewer than 2^30 entries")
-        self.wtab = wa.build(np.int32)
-        self.btab = ba.build(np.int32, 2) if ba.size else np.full((4, 2), -1, dtype=np.int32)
-        self.ktab = kta.build(np.int32, 4)
-        self.ntab = nta.build(np.int32, 4, fill=0)
-        for p in self.prods.values():
-            p.wtab = None            # the arena's table holds the only copy from here on
-        wa.pieces = []
-        self.utab1 = self._build_unpack_table()
-
-    def _build_unpack_table(self):
-        """int32 [n_params]: (index in the packed-gradient buffer) << 1 of every parameter element, -1 for the layout's padding."""
-        L, cfg = self.layout, self.cfg
-        ia = L.index_array
-        tab = np.full(L.n_params, -1, dtype=np.int32)
-        total = [0]
-
-        def put(pidx, gidx):
-            pidx = np.asarray(pidx, dtype=np.int64).reshape(-1)
-            gidx = np.asarray(gidx, dtype=np.int64).reshape(-1)
-            tab[pidx] = (gidx << 1).astype(np.int32)
-            total[0] += pidx.size
-
-        for p in self.prods.values():
-            if p.dw_off is None:
-                continue
-            w = self.wtab[p.w_off:p.w_off + p.Npad * p.K]
-            m = np.flatnonzero(w >= 0)
-            put(w[m] >> 1, p.dw_off + m)
-            b = p.bias[:, 0]
-            m = np.flatnonzero(b >= 0)
-            put(b[m] >> 1, p.db_off + m)
-        c0 = cfg.ci
-        put(ia("encoder.0.main.0.weight"), self.enc0_goff + np.arange(ENC_TAPS * c0))
-        put(ia("encoder.0.main.0.bias"), self.enc0_goff + ENC_TAPS * c0 + np.arange(c0))
-        for nm in self.norms.values():
-            put(ia(nm["pre"] + "1.weight"), nm["goff"] + np.arange(nm["C"]))
-            put(ia(nm["pre"] + "1.bias"), nm["goff"] + nm["C"] + np.arange(nm["C"]))
-        put(ia("out.0.weight"), self.out_goff + np.arange(c0 + 1))
-        put(ia("out.0.bias"), self.out_goff + c0 + 1)
-        used = np.zeros(L.n_params, dtype=bool)
-        for name in L.param_names:
-            off, shape = L.param_off[name]
-            used[off:off + (int(np.prod(shape)) if len(shape) else 1)] = True
-        # as many entries as parameter elements, every element has one, none outside: exactly one each
-        assert total[0] == int(used.sum()) and (tab[used] >= 0).all() and (tab[~used] < 0).all(), \
-            "every WavUnet parameter has exactly one packed-gradient entry"
-        self.unpack_entries = (tab >= 0).astype(np.int8)
-        return tab
+        c0 = ci
+        self._assemble(extra=[(ia("encoder.0.main.0.weight"), self.enc0_goff + np.arange(ENC_TAPS * c0)),
+                              (ia("encoder.0.main.0.bias"), self.enc0_goff + ENC_TAPS * c0 + np.arange(c0)),
+                              (ia("out.0.weight"), self.out_goff + np.arange(c0 + 1)),
+                              (ia("out.0.bias"), self.out_goff + c0 + 1)])
 
 
-class WavUnetDeviceTables:
-    def __init__(self, st: WavUnetStatic, device):
-        f = lambda a: torch.from_numpy(a).to(device)
-        self.wtab, self.btab, self.ntab, self.utab1 = f(st.wtab), f(st.btab), f(st.ntab), f(st.utab1)
-        self.tensor_offsets = f(st.layout.tensor_offsets)
-        self.wpack = torch.zeros(st.n_wpack, dtype=BF16, device=device)
-        self.bpack = torch.zeros(st.n_bpack, dtype=torch.float32, device=device)
+WavUnetDeviceTables = ProdDeviceTables
 
 
 def valid_lengths(T, n):
@@ -256,9 +155,8 @@ def valid_lengths(T, n):
     return lo, hi
 
 
-class WavUnetWorkspace(GemmWorkspace):
+class WavUnetWorkspace(ProdWorkspace):
     def __init__(self, st: WavUnetStatic, tables: WavUnetDeviceTables, B, T, device):
-        super().__init__()
         cfg = st.cfg
         n = cfg.n
         if T % 2 ** n or T // 2 ** n < 2:
@@ -268,70 +166,24 @@ class WavUnetWorkspace(GemmWorkspace):
                              + (f" and {hi}" if hi != lo else ""))
         if B < 1 or B > 65535:
             raise SehipError(f"WavUnet: batch size B={B} must be in 1 .. 65535")
-        self.st, self.tb, self.B, self.T, self.device = st, tables, B, T, device
+        self.B, self.T = B, T
         self.lens = [T >> l for l in range(n + 1)]
+        super().__init__(st, tables, B, self.lens, [1] * (n + 1), device)
         lib = _lib.lib()
-        self.bufs = {}
-        for name, (level, c) in st.buffers.items():
-            self.bufs[name] = Buf(torch.zeros(B, self.lens[level], 1, c, dtype=BF16, device=device), self.lens[level], 1, c)
         self.out = torch.zeros(B, 1, T, dtype=torch.float32, device=device)
-        self.coef = {k: torch.zeros(nm["C"], 4, dtype=torch.float32, device=device) for k, nm in st.norms.items()}
-        self.bcoef = {k: torch.zeros(nm["C"], 4, dtype=torch.float32, device=device) for k, nm in st.norms.items()}
-        # one row of partial sums per workgroup; every layer its own (the op-local tests read them back)
-        self.part = {k: torch.zeros(int(lib.sehip_wun_bn_scratch_floats(B * self.lens[nm["level"]], nm["C"])), dtype=torch.float32, device=device)
-                     for k, nm in st.norms.items()}
-        self.bpart = {k: torch.zeros_like(v) for k, v in self.part.items()}
         self.enc0_scratch = torch.zeros(int(lib.sehip_wun_enc0_wgrad_scratch_floats(B, T, cfg.ci)), dtype=torch.float32, device=device)
         self.out_scratch = torch.zeros(int(lib.sehip_wun_out_bwd_scratch_floats(B * T, cfg.ci)), dtype=torch.float32, device=device)
-        self.gpack = torch.zeros(st.n_gpack, dtype=torch.float32, device=device)
         self.wav = None
         self.training = True
-        self._bwd_clean = False
-        self.side = self._side_stream = self._new_side_stream(device)
-        self._bind()
 
-    def _view(self, name, pair):
+    def _src_view(self, s):
+        """a source is (buffer, pair view?): the pair view of [B][T][C] is [B][T / 2][2 C], whose channels 0 .. C-1 are the even frames"""
+        name, pair = s
         b = self.bufs[name]
         if not pair:
-            return b.Tst, b.C
+            return b.ptr, b.Tst, 1, b.C
         assert b.Tst % 2 == 0
-        return b.Tst // 2, 2 * b.C
-
-    def _bind(self):
-        st, tb, B = self.st, self.tb, self.B
-        self.desc = {}
-        kt = st.ktab.copy()
-        for p in st.prods.values():
-            bind_chunk_table(st.ktab, kt, p.kt_off, p.K // 8, [(1, self._view(*s)[1]) for s in p.srcs])
-        self.ktab_dev = torch.from_numpy(kt).to(self.device)
-        for name, p in st.prods.items():
-            d = CGemmDesc()
-            tt = self.lens[p.level]
-            for q, s in enumerate(p.srcs):
-                sT, sC = self._view(*s)
-                assert sT == tt, (name, s, sT, tt)
-                d.src[q].ptr, d.src[q].T, d.src[q].F, d.src[q].C, d.src[q].tlo, d.src[q].thi = self.bufs[s[0]].ptr, sT, 1, sC, 0, sT
-            for q, (bname, cols) in enumerate(p.dsts):
-                ob = self.bufs[bname]
-                assert ob.Tst == tt and ob.C == cols, (name, bname)
-                d.dst[q].ptr, d.dst[q].T, d.dst[q].F, d.dst[q].C = ob.ptr, tt, 1, ob.C
-                d.dst[q].toff, d.dst[q].fmul, d.dst[q].fadd, d.dst[q].tmul, d.dst[q].is_f32 = 0, 1, 0, 1, 0
-            d.ktab = self.ktab_dev.data_ptr() + 16 * p.kt_off
-            d.ntab = tb.ntab.data_ptr() + 16 * p.nt_off
-            d.W = tb.wpack.data_ptr() + 2 * p.w_off
-            if p.b_off is not None:
-                d.bias = tb.bpack.data_ptr() + 4 * p.b_off
-            d.M, d.N, d.Npad, d.K = B * tt, p.N, p.Npad, p.K
-            d.TT, d.J, d.fmul, d.tmul = tt, 1, 1, 1
-            self.desc[name] = d
-            if p.dw_off is not None:
-                w = CGemmDesc.from_buffer_copy(d)
-                w.dW = self.gpack.data_ptr() + 4 * p.dw_off
-                w.dbias = self.gpack.data_ptr() + 4 * p.db_off
-                gb = self.bufs[p.dout]
-                assert gb.Tst == tt and gb.C == p.N, (name, p.dout)
-                w.dst[0].ptr = gb.ptr
-                self.desc[name + ".wg"] = w
+        return b.ptr, b.Tst // 2, 1, 2 * b.C
 
     # ---- launches (gemm, wgrad: GemmWorkspace) ------------------------------------------------------------------------
     def _norm_coef(self, key, params, buffers, nbt, training):
@@ -341,9 +193,9 @@ class WavUnetWorkspace(GemmWorkspace):
         rows = self.B * y.Tst
         if training:
             call("sehip_wun_bn_stats", y.ptr, rows, nm["C"], ptr(self.part[key]), stream())
-        call("sehip_wun_bn_finalize", ptr(self.part[key]), y.ptr, self._pp(params, pre + "1.weight"), self._pp(params, pre + "1.bias"),
-             buffers.data_ptr() + 4 * L.buffer_off[pre + "1.running_mean"][0], buffers.data_ptr() + 4 * L.buffer_off[pre + "1.running_var"][0],
-             nbt.data_ptr() + 8 * L.nbt_idx[pre + "1.num_batches_tracked"], rows, nm["C"], BN_EPS, BN_MOMENTUM, 1 if training else 0,
+        call("sehip_wun_bn_finalize", ptr(self.part[key]), y.ptr, self._pp(params, pre + "weight"), self._pp(params, pre + "bias"),
+             buffers.data_ptr() + 4 * L.buffer_off[pre + "running_mean"][0], buffers.data_ptr() + 4 * L.buffer_off[pre + "running_var"][0],
+             nbt.data_ptr() + 8 * L.nbt_idx[pre + "num_batches_tracked"], rows, nm["C"], BN_EPS, BN_MOMENTUM, 1 if training else 0,
              ptr(self.coef[key]), stream())
         return rows
 
@@ -361,14 +213,11 @@ class WavUnetWorkspace(GemmWorkspace):
 
     def forward(self, wav, params, buffers, nbt, training=True):
         """wav [B, 1, T] fp32 on device -> self.out [B, 1, T]."""
-        st, cfg, b, tb = self.st, self.st.cfg, self.bufs, self.tb
+        cfg, b = self.st.cfg, self.bufs
         B, T, n, c0 = self.B, self.T, cfg.n, cfg.ci
         pp = lambda nme: self._pp(params, nme)
         self.wav, self.training = wav, bool(training)
-        call("sehip_zero_regions", ptr(self.gpack), self.gpack.numel() * 4, None, 0, None, 0, None, 0, stream())
-        self._bwd_clean = True
-        call("sehip_pack_bf16", ptr(params), ptr(tb.wtab), st.n_wpack, ptr(tb.wpack), stream())
-        call("sehip_pack_f32", ptr(params), ptr(tb.btab), st.n_bpack, ptr(tb.bpack), stream())
+        self._prologue(params)
         call("sehip_wun_enc0_fwd", ptr(wav), pp("encoder.0.main.0.weight"), pp("encoder.0.main.0.bias"), B, T, c0, b["e0.y"].ptr, stream())
         for l in range(n):
             k = f"e{l}"
@@ -394,14 +243,11 @@ class WavUnetWorkspace(GemmWorkspace):
         """dout [B, 1, T] fp32 -> flat parameter gradients (overwritten)."""
         if not self.training:
             raise SehipError("WavUnet.backward in eval mode: the backward pass is built for batch statistics only (call model.train())")
-        st, cfg, b, tb = self.st, self.st.cfg, self.bufs, self.tb
+        st, cfg, b = self.st, self.st.cfg, self.bufs
         B, T, n, c0 = self.B, self.T, cfg.n, cfg.ci
         pp = lambda nme: self._pp(params, nme)
         gp = lambda off: self.gpack.data_ptr() + 4 * off
-        if not self._bwd_clean:            # a second backward pass over the same forward
-            self.gpack.zero_()
-        self._bwd_clean = False
-        self._chain_dirty = True
+        self._begin_backward()
         call("sehip_wun_out_bwd", ptr(dout), ptr(self.out), b["zl"].ptr, ptr(self.wav), pp("out.0.weight"), B * T, c0, b[f"d{n - 1}.dz"].ptr,
              gp(st.out_goff), gp(st.out_goff + c0 + 1), ptr(self.out_scratch), stream())
         for i in range(n - 1, -1, -1):
@@ -423,11 +269,4 @@ class WavUnetWorkspace(GemmWorkspace):
                 self.gemm(k + ".dg")
         call("sehip_wun_enc0_wgrad", b["e0.dy"].ptr, ptr(self.wav), B, T, c0, gp(st.enc0_goff), gp(st.enc0_goff + ENC_TAPS * c0),
              ptr(self.enc0_scratch), stream())
-        self.join_side()
-        np_ = st.layout.n_params
-        if tail is not None:      # FlatOptimizer's accumulators: the un-pack also takes the clipping norm / metric sums
-            call("sehip_unpack_grad1_sums", ptr(self.gpack), ptr(tb.utab1), np_, ptr(grads), tail[2], tail[3], tail[0], tail[1], tail[4],
-                 None, stream())
-        else:
-            call("sehip_unpack_grad1", ptr(self.gpack), ptr(tb.utab1), np_, ptr(grads), stream())
-        return grads
+        return self._unpack(grads, tail)

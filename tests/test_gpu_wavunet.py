@@ -1,6 +1,6 @@
 """GPU: Wave-U-Net (`wav-unet`) on the HIP path (csrc/wavunet.hip + the implicit-GEMM engine, sehip/plan_wavunet.py).
 
-1. op-local: after one forward + backward pass of each fixture (SEHIP_WUN_KEEP_GRADS=1) EVERY launch is recomputed in float64 from the
+1. op-local: after one forward + backward pass of each fixture (every layer owns its buffers) EVERY launch is recomputed in float64 from the
    operands the kernel itself read, taken back from the workspace;
 2. the whole chain against vectors of the imported reference (tests/golden/wavunet_*.npz): the bound is measured, 2 x the deviation of the
    bf16-storage restatement (tests/wavunet_ref.py under Bf16Sim) from the same vectors, computed on the CPU in the same test;
@@ -76,20 +76,12 @@ def run_kept(tag):
         return _RUN[tag]
     from sehip.model import WavUnet
     fx = fixture(tag)
-    old = os.environ.get("SEHIP_WUN_KEEP_GRADS")
-    os.environ["SEHIP_WUN_KEEP_GRADS"] = "1"
-    try:
-        model = WavUnet(**model_kw(tag))
-        model.load_state_dict(fx["sd"])
-        model.cuda().train()
-        est = model(fx["mix"].cuda())
-        (est * fx["G"].cuda()).sum().backward()
-        torch.cuda.synchronize()
-    finally:
-        if old is None:
-            del os.environ["SEHIP_WUN_KEEP_GRADS"]
-        else:
-            os.environ["SEHIP_WUN_KEEP_GRADS"] = old
+    model = WavUnet(**model_kw(tag))
+    model.load_state_dict(fx["sd"])
+    model.cuda().train()
+    est = model(fx["mix"].cuda())
+    (est * fx["G"].cuda()).sum().backward()
+    torch.cuda.synchronize()
     ws = model.workspace(fx["mix"].shape[0], fx["mix"].shape[-1])
     grads = {k: p.grad.detach().cpu().clone() for k, p in model.named_parameters()}
     _RUN[tag] = (model, ws, est.detach().cpu(), grads)
