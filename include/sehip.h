@@ -581,6 +581,25 @@ long sehip_ctn_cln_bwd_scratch_floats(int M, int K, int C);
 int sehip_ctn_cln_bwd(const void* g, const void* h, const float* slope, const float* gamma, const float* beta, const float* Wd, int P,
                       int dilation, int dw, int causal, int M, int K, int C, float* gch, void* dh, float* dslope, float* scratch,
                       void* stream);
+/* ---- causal=True, norm_type='cLN' chunk by chunk (csrc/tasnet_stream.hip; sehip/model/conv_tasnet_stream.py): S streams, Kc frames
+ * per call from Kc h new samples per stream (h = L/2).  pos [S] int32: global index of the first frame of the coming call (-1 on a
+ * fresh stream: that frame is built from the zero carry and contributes nothing; depthwise taps with a negative global index are
+ * absent).  Every piece of carried state exists twice and phase [1] int32 (0 / 1) names the current half: a launch reads half `phase`
+ * and writes half `phase ^ 1`, so no launch overwrites what it reads; sehip_ctns_advance flips it at the end of the chunk.
+ *      encoder : x fp32 [S][ac][Kc h], carry fp32 [2][S][ac][h] -> w fp32 [S][Kc][N], cln bf16 [S][Kc][N] (the arithmetic of
+ *                sehip_ctn_encoder_fwd's wave-per-frame kernel), and the other half's carry
+ *      dwconv  : h1 bf16 [S][Kc][C], hist bf16 [2][S][(P - 1) d][C] -> h2 bf16 [S][Kc][C] = causal depthwise conv of cLN(PReLU(.))
+ *                over history | chunk (a frame's arithmetic is sehip_ctn_cln_dwconv_fwd's, causal), and the other half's history
+ *      decoder : w, mask bf16 [S][Kc][Cs N] (mask logits, or the output of sehip_ctn_mask_softmax_fwd), tail fp32 [2][S][Cs][ac][h]
+ *                -> out fp32 [S][Cs][ac][Kc h], every sample stored once (no atomics, no clearing), and the other half's tail
+ *      advance : pos[s] += Kc, phase ^= 1 */
+int sehip_ctns_encoder(const float* x, float* carry, const int* phase, const float* U, const float* gamma, const float* beta, int S, int ac,
+                       int Kc, int N, int L, float* w, void* cln_bf16, void* stream);
+int sehip_ctns_dwconv(const void* h1, void* hist, const int* phase, const int* pos, const float* slope1, const float* gamma,
+                      const float* beta, const float* Wd, int P, int dilation, int S, int Kc, int C, void* h2, void* stream);
+int sehip_ctns_decoder(const float* w, const void* mask_bf16, const float* V, float* tail, const int* phase, const int* pos, int S, int Kc,
+                       int N, int L, int ac, int Cs, float* out, void* stream);
+int sehip_ctns_advance(int* pos, int* phase, int S, int Kc, void* stream);
 /* mask_nonlinear='softmax' (src/model/conv_tasnet.py:298-299: F.softmax(score, dim=1) over the Cs <= 8 sources): score / out bf16
  * [rows = M * K][Cs][N].  The decoder entry points below take `out` as their mask logits (their relu is the identity on it); what
  * sehip_ctn_decoder_bwd writes for it is the gradient of the mask, which sehip_ctn_mask_softmax_bwd turns into the gradient of the

@@ -151,6 +151,10 @@ _PROTOS = {
     "sehip_ctn_mask_softmax_bwd": [P, P, L, I, I, P],
     "sehip_ctn_decoder_fwd": [P, P, P, I, I, I, I, I, I, I, P, P],
     "sehip_ctn_decoder_bwd": [P, P, P, P, I, I, I, I, I, I, I, P, P, P, P, P],
+    "sehip_ctns_encoder": [P, P, P, P, P, P, I, I, I, I, I, P, P, P],
+    "sehip_ctns_dwconv": [P, P, P, P, P, P, P, P, I, I, I, I, I, P, P],
+    "sehip_ctns_decoder": [P, P, P, P, P, P, I, I, I, I, I, I, P, P],
+    "sehip_ctns_advance": [P, P, I, I, P],
     "sehip_dmx_prep": [P, I, I, I, I, I, I, I, I, P, I, I, P, P, P, P],
     "sehip_dmx_post": [P, P, I, I, I, L, I, I, I, P, I, I, P, P],
     "sehip_dmx_post_bwd": [P, P, I, I, I, L, I, I, I, P, I, I, P, P],

@@ -49,6 +49,45 @@ __device__ __forceinline__ void ld8f(const float* __restrict__ p, float (&v)[8])
     v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
 }
 
+// ---- per-frame (cLN) kernels: csrc/tasnet_cln.hip and the chunked streamer's csrc/tasnet_stream.hip share these, so a frame's
+// arithmetic is the same code in both ----
+// group of G lanes (a power of two <= 64, aligned) -> the sum over the group in every lane
+__device__ __forceinline__ float group_sum(float v, int G) {
+    for (int o = 1; o < G; o <<= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ void group_sum2(float& a, float& b, int G) {
+    for (int o = 1; o < G; o <<= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
+}
+
+// Thread layout: lane group of G per frame, thread owns piece q = tid % G (idle when q >= nq) of frames bx*rpb + tid/G, stepping by
+// gridDim.x*rpb with rpb = 256/G.  The frame loop is uniform over the workgroup (the shuffles run with all lanes on).
+struct FrameMap { int q, c0, rsub, rpb, G; bool act; };
+__device__ __forceinline__ FrameMap frame_map(int nq) {
+    FrameMap f;
+    f.G = 1;
+    while (f.G < nq) f.G <<= 1;
+    f.rpb = 256 / f.G;
+    f.q = threadIdx.x & (f.G - 1);
+    f.rsub = threadIdx.x / f.G;
+    f.act = f.q < nq;
+    f.c0 = (f.act ? f.q : 0) * 8;
+    return f;
+}
+
+// v = PReLU(x) -> centred values d = v - mean and 1/sigma of the frame (idle lanes: x = 0 in, d forced to 0)
+__device__ __forceinline__ float cln_center(const C8& x, float a, bool act, int G, float invC, float (&d)[8]) {
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { d[j] = prelu(x.v[j], a); s += d[j]; }
+    const float mean = group_sum(s, G) * invC;
+    float q = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { d[j] = act ? d[j] - mean : 0.f; q += d[j] * d[j]; }
+    const float var = group_sum(q, G) * invC;
+    return 1.f / sqrtf(var + CTN_EPS);
+}
+
 static int ctn_check(const char* who, int M, int K, int C) {
     SEHIP_REQUIRE(M > 0 && K > 0, "%s: empty input", who);
     SEHIP_REQUIRE(C >= 8 && C <= 512 && (C & 7) == 0, "%s: channels C=%d must be a multiple of 8 in [8, 512]", who, C);

@@ -23,42 +23,7 @@
 #include "det.h"
 #include "ctn.h"
 
-// group of G lanes (a power of two <= 64, aligned) -> the sum over the group in every lane
-__device__ __forceinline__ float group_sum(float v, int G) {
-    for (int o = 1; o < G; o <<= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ void group_sum2(float& a, float& b, int G) {
-    for (int o = 1; o < G; o <<= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
-}
-
-// Thread layout: lane group of G per frame, thread owns piece q = tid % G (idle when q >= nq) of frames bx*rpb + tid/G, stepping by
-// gridDim.x*rpb with rpb = 256/G.  The frame loop is uniform over the workgroup (the shuffles run with all lanes on).
-struct FrameMap { int q, c0, rsub, rpb, G; bool act; };
-__device__ __forceinline__ FrameMap frame_map(int nq) {
-    FrameMap f;
-    f.G = 1;
-    while (f.G < nq) f.G <<= 1;
-    f.rpb = 256 / f.G;
-    f.q = threadIdx.x & (f.G - 1);
-    f.rsub = threadIdx.x / f.G;
-    f.act = f.q < nq;
-    f.c0 = (f.act ? f.q : 0) * 8;
-    return f;
-}
-
-// v = PReLU(x) -> centred values d = v - mean and 1/sigma of the frame (idle lanes: x = 0 in, d forced to 0)
-__device__ __forceinline__ float cln_center(const C8& x, float a, bool act, int G, float invC, float (&d)[8]) {
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { d[j] = prelu(x.v[j], a); s += d[j]; }
-    const float mean = group_sum(s, G) * invC;
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { d[j] = act ? d[j] - mean : 0.f; q += d[j] * d[j]; }
-    const float var = group_sum(q, G) * invC;
-    return 1.f / sqrtf(var + CTN_EPS);
-}
+// (group_sum, FrameMap and cln_center -- the lane-group sums, the thread layout and a frame's moments -- are in ctn.h)
 
 __global__ __launch_bounds__(256) void ctn_cln_apply_kernel(const bf16_raw* __restrict__ h, const float* __restrict__ slope,
                                                             const float* __restrict__ gamma, const float* __restrict__ beta, int K, int C,
