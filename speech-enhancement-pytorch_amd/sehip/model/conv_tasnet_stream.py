@@ -28,7 +28,7 @@ import ctypes as C
 import torch
 
 from .._lib import SehipError, call, ptr, stream, stream_scope
-from ..plan import BF16, CGemmDesc, bind_chunk_table
+from ..gemmdesc import BF16, fill_desc, row_ptr, upload_chunk_table
 from .conv_tasnet import ConvTasNet
 
 
@@ -124,27 +124,16 @@ class ConvTasNetStreamer:
 
     def _bind(self):
         st, S, Kc = self.st, self.streams, self.chunk_frames
-        kt = st.ktab.copy()
-        for name in self._names():
-            s = st.specs[name]
-            bind_chunk_table(st.ktab, kt, s.kt_off, s.K // 8, [(1, self._buf(b).shape[-1]) for b, _ in s.srcs])
-        self.ktab = torch.from_numpy(kt).to(self.device)
+        self.ktab = upload_chunk_table(st.ktab, [st.specs[name] for name in self._names()],
+                                       lambda s: [(1, self._buf(b).shape[-1]) for b, _ in s.srcs], self.device)
         self.desc = {}
         for name in self._names():
             s = st.specs[name]
-            d = CGemmDesc()
             b, o = self._buf(s.srcs[0][0]), self._buf(s.dsts[0][0])
             bc, oc = b.shape[-1], o.shape[-1]
-            d.src[0].ptr, d.src[0].T, d.src[0].F, d.src[0].C, d.src[0].tlo, d.src[0].thi = b.data_ptr(), Kc, 1, bc, 0, Kc
-            d.dst[0].ptr, d.dst[0].T, d.dst[0].F, d.dst[0].C = o.data_ptr(), Kc, 1, oc
-            d.dst[0].toff, d.dst[0].fmul, d.dst[0].fadd, d.dst[0].is_f32, d.dst[0].tmul = 0, 1, 0, 0, 1
-            d.ktab = self.ktab.data_ptr() + 16 * s.kt_off
-            d.ntab = self.ntab.data_ptr() + 16 * s.nt_off
-            d.W = self.wpack.data_ptr() + 2 * s.w_off
-            d.M, d.N, d.Npad, d.K = S * Kc, s.N, s.Npad, s.K
-            d.TT, d.J, d.fmul, d.tmul = Kc, 1, 1, 1
-            if s.res is not None:
-                d.res = self._buf(s.res).data_ptr()
+            d = fill_desc([(b.data_ptr(), Kc, 1, bc, 0, Kc)], [(o.data_ptr(), Kc, 1, oc, 0, 1, 0, 1, 0)], row_ptr(self.ktab, s.kt_off),
+                          row_ptr(self.ntab, s.nt_off), row_ptr(self.wpack, s.w_off), None, S * Kc, s.N, s.Npad, s.K, Kc, 1, 1, 1,
+                          self._buf(s.res).data_ptr() if s.res is not None else None)
             d.dense_rows = 1 if (bc == s.K and oc == s.Npad == s.N) else 0      # (as plan_tasnet.TasNetWorkspace._bind)
             self.desc[name] = d
 

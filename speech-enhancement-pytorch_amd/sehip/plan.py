@@ -2,12 +2,14 @@
 descriptors and the launch sequences of forward and backward.
 
 Everything numeric runs in libsehip (HIP); this module only does bookkeeping with numpy at construction time:
-  * ParamLayout  -- the reference's state_dict schema (src/model/dccrn.py:62-137) laid out in
-                    ONE flat fp32 buffer (parameters) + one flat fp32 buffer (BatchNorm running statistics).
+  * DCCRNConfig  -- the reference's state_dict schema (src/model/dccrn.py:62-137), which gemmdesc.ParamLayout lays
+                    out in ONE flat fp32 buffer (parameters) + one flat fp32 buffer (BatchNorm running statistics).
   * pack tables  -- how the GEMM-side bf16 weights / fp32 biases are gathered from the flat parameters and how the
                     packed gradients fold back (complex block matrix, tap order, skip-concat order, LSTM permutations).
   * descriptors  -- sehip_gemm_desc instances (include/sehip.h) for every conv / deconv / linear product,
                     its dgrad and its wgrad.
+The engine's host types (CGemmDesc, ParamLayout, Arena, the table helpers, the descriptor binder and the un-pack table builder) are
+gemmdesc.py's and are importable from here as before; GemmSpec, DCCRN's product record, is borrowed by DCUnet and ConvTasNet.
 Channel-last layout [B][T][F][C]; decoder tensors that feed a BatchNorm keep the extra first frame the reference
 drops after the BatchNorm (src/model/dccrn.py:193-196), i.e. they store T+1 frames and logical frame t lives at t+1.
 """
@@ -21,36 +23,10 @@ import torch
 from . import _lib
 from ._lib import call, ptr, stream, SehipError
 from . import ops
-from .workspace import Buf, GemmWorkspace, gather_ordered_device_tables, gather_ordered_unpack_table      # (Buf, gather_ordered_unpack_table: importable from here as before)
-
-BF16 = torch.bfloat16
-
-
-# --------------------------------------------------------------------------------------------------
-# ctypes mirrors of include/sehip.h
-# --------------------------------------------------------------------------------------------------
-class CSrc(C.Structure):
-    _fields_ = [("ptr", C.c_void_p), ("T", C.c_int32), ("tlo", C.c_int32), ("thi", C.c_int32), ("F", C.c_int32),
-                ("C", C.c_int32), ("pad_", C.c_int32)]
-
-
-class CDst(C.Structure):
-    _fields_ = [("ptr", C.c_void_p), ("T", C.c_int32), ("F", C.c_int32), ("C", C.c_int32), ("toff", C.c_int32),
-                ("fmul", C.c_int32), ("fadd", C.c_int32), ("is_f32", C.c_int32), ("tmul", C.c_int32)]
-
-
-class CGemmDesc(C.Structure):
-    _fields_ = [("src", CSrc * 4), ("dst", CDst * 2), ("ktab", C.c_void_p), ("ntab", C.c_void_p), ("W", C.c_void_p),
-                ("bias", C.c_void_p), ("dW", C.c_void_p), ("dbias", C.c_void_p), ("M", C.c_int32), ("N", C.c_int32),
-                ("Npad", C.c_int32), ("K", C.c_int32), ("TT", C.c_int32), ("J", C.c_int32), ("fmul", C.c_int32),
-                ("tmul", C.c_int32), ("cv_nf", C.c_int32), ("cv_fadd", C.c_int32), ("cv_toff", (C.c_int32 * 2) * 2),
-                ("res", C.c_void_p), ("stats", C.c_void_p), ("stats_cr", C.c_int32), ("cv2_nkt", C.c_int32), ("cv2_nf", C.c_int32),
-                ("cv2_fadd", C.c_int32), ("cv2_t0", C.c_int32), ("w_tiled", C.c_int32), ("wg_hint", C.c_int32), ("dense_rows", C.c_int32),
-                ("dw_split_stride", C.c_int64),
-                ("bn_dz", C.c_void_p), ("bn_y", C.c_void_p), ("bn_coef", C.c_void_p), ("bn_bcoef", C.c_void_p),
-                ("bn_slope", C.c_void_p),
-                ("bnr_y", C.c_void_p), ("bnr_coef", C.c_void_p), ("bnr_slope", C.c_void_p), ("bnr_part", C.c_void_p),
-                ("gln_stats", C.c_void_p), ("gln_slope", C.c_void_p)]
+# (every name that moved to gemmdesc.py stays importable from here, used below or not)
+from .gemmdesc import (BF16, CSrc, CDst, CGemmDesc, ParamLayout, Arena, enc_entry, npad_of, round_up, dense_ntab, wide_chunks, pad_ktab,
+                       bind_chunk_table, upload_chunk_table, row_ptr, fill_desc, wgrad_twin, UnpackTable, check_unpack_coverage)
+from .workspace import Buf, GemmDeviceTables, GemmWorkspace, gather_ordered_unpack_table      # (Buf, gather_ordered_unpack_table: importable from here as before)
 
 
 # The gradient that arrives over the skip connection is added by the dgrad product that writes the encoder output's gradient
@@ -69,20 +45,6 @@ BWD_REPLICAS = int(os.environ.get("SEHIP_BWD_REPLICAS", "8"))
 PARALLEL_HEAD = not os.environ.get("SEHIP_NO_PARALLEL_HEAD")      # weight packing + gradient clearing beside the STFT (A/B switch)
 L2_GRAPH_EPOCH = 65535       # granule-tag epoch of the fused LSTM launches inside captured graphs; eager calls use 1 .. 65534
 TILE_WEIGHTS = not any(os.environ.get(k) for k in ("SEHIP_NO_CONV_V3", "SEHIP_NO_PATCH", "SEHIP_NO_TILE_WEIGHTS"))
-
-
-def npad_of(n):
-    if n <= 16:
-        return 16
-    if n <= 32:
-        return 32
-    if n <= 64:
-        return 64
-    return (n + 127) // 128 * 128
-
-
-def round_up(x, m):
-    return (x + m - 1) // m * m
 
 
 # --------------------------------------------------------------------------------------------------
@@ -190,62 +152,9 @@ class DCCRNConfig:
         return out
 
 
-class ParamLayout:
-    def __init__(self, cfg):
-        self.cfg = cfg
-        self.specs = cfg.param_specs()
-        self.param_off, self.buffer_off, self.nbt_idx = {}, {}, {}
-        po = bo = 0
-        self.param_names, self.buffer_names, self.nbt_names = [], [], []
-        for name, shape, kind in self.specs:
-            n = int(np.prod(shape)) if len(shape) else 1
-            if kind == "param":
-                self.param_off[name] = (po, shape)
-                self.param_names.append(name)
-                po += round_up(n, 4)
-            elif kind == "buffer":
-                self.buffer_off[name] = (bo, shape)
-                self.buffer_names.append(name)
-                bo += round_up(n, 4)
-            else:
-                self.nbt_idx[name] = len(self.nbt_names)
-                self.nbt_names.append(name)
-        self.n_params = po
-        self.n_buffers = bo
-        # tensor boundaries for the reference's per-tensor grad_norm metric (src/solver.py:494-498)
-        offs = [self.param_off[n][0] for n in self.param_names] + [po]
-        self.tensor_offsets = np.asarray(offs, dtype=np.int64)
-
-    # ComplexBatchNorm field -> (tensor, element offset inside it); None = the field does not exist (real BatchNorm2d: no cross terms)
-    _REAL_BN = {"1.Wrr": ("1.weight", 0), "1.Wii": ("1.weight", 1), "1.Br": ("1.bias", 0), "1.Bi": ("1.bias", 1), "1.Wri": None,
-                "1.RMr": ("1.running_mean", 0), "1.RMi": ("1.running_mean", 1), "1.RVrr": ("1.running_var", 0),
-                "1.RVii": ("1.running_var", 1), "1.RVri": None}
-
-    def bn_field(self, pre, k, cr):
-        """(name, element offset) of ComplexBatchNorm field k ("1.Wrr", "1.RMr", ...) of layer `pre`, or None.  With use_cbn=False the
-        layer is an nn.BatchNorm2d over 2 cr channels: its weight / bias / running statistics are the real and imaginary halves."""
-        if getattr(self.cfg, "use_cbn", True) or k not in self._REAL_BN:
-            return pre + k, 0
-        m = self._REAL_BN[k]
-        return None if m is None else (pre + m[0], m[1] * cr)
-
-    def index_array(self, name):
-        off, shape = self.param_off[name]
-        n = int(np.prod(shape))
-        return (off + np.arange(n, dtype=np.int64)).reshape(shape)
-
-
 # --------------------------------------------------------------------------------------------------
 # table helpers
 # --------------------------------------------------------------------------------------------------
-def enc_entry(idx, neg):
-    """(index<<1)|neg, -1 where idx < 0."""
-    idx = np.asarray(idx, dtype=np.int64)
-    neg = np.broadcast_to(np.asarray(neg, dtype=np.int64), idx.shape)
-    e = (idx << 1) | neg
-    return np.where(idx < 0, -1, e).astype(np.int32)
-
-
 def complex_block(wr, wi, transposed):
     """Index/sign arrays of the real block matrix of a complex conv.
 
@@ -263,84 +172,6 @@ def complex_block(wr, wi, transposed):
         idx[:a, b:], idx[a:, :b] = wi, wi
         neg[a:, :b] = 1
     return idx, neg
-
-
-class Arena:
-    """Grows a list of numpy pieces that end up as one flat device buffer; returns element offsets."""
-
-    def __init__(self, align):
-        self.pieces, self.size, self.align = [], 0, align
-
-    def add(self, arr):
-        off = self.size
-        self.pieces.append((off, arr))
-        self.size += round_up(arr.shape[0], self.align)
-        return off
-
-    def reserve(self, n):
-        off = self.size
-        self.size += round_up(n, self.align)
-        return off
-
-    def build(self, dtype, width=None, fill=-1):
-        shape = (self.size,) if width is None else (self.size, width)
-        out = np.full(shape, fill, dtype=dtype)
-        for off, arr in self.pieces:
-            out[off:off + arr.shape[0]] = arr
-        return out
-
-
-class Gemm:
-    """One implicit-GEMM problem: descriptor + the pieces needed to (re)bind pointers."""
-
-    def __init__(self, name):
-        self.name = name
-        self.desc = CGemmDesc()
-        self.w_off = None      # offset in packed bf16 weights
-        self.b_off = None      # offset in packed fp32 bias
-        self.dw_off = None     # offset in packed-gradient buffer
-        self.db_off = None
-        self.ktab = None
-        self.ntab = None
-
-
-def dense_ntab(n, npad, dst=0, base=0):
-    t = np.zeros((npad // 4, 4), dtype=np.int32)
-    for q in range(npad // 4):
-        t[q] = (dst, base + 4 * q, max(0, min(4, n - 4 * q)), 0)
-    return t
-
-
-def wide_chunks(src, toff, fadd, c0, cn):
-    """chunks covering channels [c0, c0+cn) of one source row."""
-    assert cn % 8 == 0 and c0 % 8 == 0
-    return [(src, toff, fadd, c0 + 8 * q) for q in range(cn // 8)]
-
-
-def pad_ktab(rows):
-    k = len(rows) * 8
-    kp = round_up(k, 64)
-    rows = rows + [(-1, 0, 0, 0)] * ((kp - k) // 8)
-    return np.asarray(rows, dtype=np.int32).reshape(-1, 4), kp
-
-
-def bind_chunk_table(src_tab, out_tab, kt_off, nchunks, geometry):
-    """Binds the chunk rows [kt_off, kt_off + nchunks) of a (src, frame offset, row offset, channel offset) table to the
-    geometry [(F, C)] of the product's sources: [src, (toff << 16) | (fadd & 0xffff), element delta, rows of a narrow chunk]
-    (sehip_kchunk in include/sehip.h)."""
-    rows = src_tab[kt_off:kt_off + nchunks]
-    out = out_tab[kt_off:kt_off + nchunks]
-    for q, (F, Cc) in enumerate(geometry):
-        m = rows[:, 0] == q
-        if not m.any():
-            continue
-        toff, fadd, coff = rows[m, 1].astype(np.int64), rows[m, 2].astype(np.int64), rows[m, 3].astype(np.int64)
-        narrow = Cc == 2
-        delta = (toff * F + fadd) * Cc + (0 if narrow else coff)
-        assert np.abs(delta).max() < 2 ** 31 and np.abs(toff).max() < 2 ** 15 and np.abs(fadd).max() < 2 ** 15
-        out[m, 1] = (((toff << 16) | (fadd & 0xffff)) & 0xffffffff).astype(np.uint32).view(np.int32)
-        out[m, 2] = delta.astype(np.int32)
-        out[m, 3] = coff.astype(np.int32) if narrow else 0
 
 
 # --------------------------------------------------------------------------------------------------
@@ -376,6 +207,16 @@ class GemmSpec:
         self.kt_off = self.nt_off = None
         self.stats_of = None   # BatchNorm prefix whose batch statistics this forward product accumulates (sehip_gemm_desc.stats)
         self.w_tiled = False   # packed weights in conv_gemm_v3's tile order (sehip_gemm_desc.w_tiled)
+
+    def put_unpack(self, ut, bias=True):
+        """this product's packed weight (and bias) gradients into the un-pack table"""
+        m = self.widx >= 0
+        ut.put(self.widx[m], self.dw_off + np.flatnonzero(m.reshape(-1)), self.wneg[m])
+        if bias and self.db_off is not None:
+            for col in (0, 1):
+                e = self.bias_pairs[:, col].astype(np.int64)
+                mm = np.flatnonzero(e >= 0)
+                ut.put(e[mm] >> 1, self.db_off + mm, e[mm] & 1)
 
     def v3_channels(self):
         """(C0, C1) of the sources when conv_gemm_v3 (csrc/conv3.hip, sehip_try_conv_gemm_v3) takes this product, else None:
@@ -820,57 +661,29 @@ class DCCRNStatic:
 
     def _build_unpack_table(self):
         L = self.layout
-        ps, gs, ns = [], [], []
+        ut = UnpackTable(L.n_params)
         for s in self.specs.values():
-            if s.dw_off is None:
-                continue
-            m = s.widx >= 0
-            ps.append(s.widx[m]); ns.append(s.wneg[m])
-            gs.append(s.dw_off + np.flatnonzero(m.reshape(-1)))
-            if s.db_off is not None:
-                for col in (0, 1):
-                    e = s.bias_pairs[:, col].astype(np.int64)
-                    mm = e >= 0
-                    ps.append(e[mm] >> 1); ns.append(e[mm] & 1)
-                    gs.append(s.db_off + np.flatnonzero(mm))
+            if s.dw_off is not None:
+                s.put_unpack(ut)
         for pre, cr in self.bn:
             for k in ("Wrr", "Wri", "Wii", "Br", "Bi"):
                 f = L.bn_field(pre, "1." + k, cr)
                 if f is None:         # (real BatchNorm2d: the cross weight does not exist; its slot of the packed gradients stays unread)
                     continue
-                ps.append(L.index_array(f[0]).reshape(-1)[f[1]:f[1] + cr]); ns.append(np.zeros(cr, np.int64))
-                gs.append(self.bn_g_off[pre][k] + np.arange(cr))
-            ps.append(L.index_array(pre + "2.weight")); ns.append(np.zeros(1, np.int64))
-            gs.append(np.asarray([self.bn_g_off[pre]["slope"]]))
-        p = np.concatenate([a.reshape(-1) for a in ps]).astype(np.int64)
-        g = np.concatenate([a.reshape(-1) for a in gs]).astype(np.int64)
-        n = np.concatenate([a.reshape(-1) for a in ns]).astype(np.int64)
-        order = np.argsort(p, kind="stable")
-        p, g, n = p[order], g[order], n[order]
-        first = np.searchsorted(p, p, side="left")
-        slot = np.arange(p.shape[0]) - first
-        assert slot.max() < 4, "a parameter feeds more than 4 packed-gradient entries"
-        tab = np.full((L.n_params, 4), -1, dtype=np.int32)
-        tab[p, slot] = ((g << 1) | n).astype(np.int32)
-        return tab
+                ut.put(L.index_array(f[0]).reshape(-1)[f[1]:f[1] + cr], self.bn_g_off[pre][k] + np.arange(cr))
+            ut.put(L.index_array(pre + "2.weight"), self.bn_g_off[pre]["slope"])
+        check_unpack_coverage(L, ut.count, what="DCCRN")
+        return ut.tab
 
 
 # --------------------------------------------------------------------------------------------------
 # dynamic part: buffers for one (batch, length), bound descriptors, launch sequences
 # --------------------------------------------------------------------------------------------------
-class DeviceTables:
-    """Device copies of the static tables (shared by every workspace of a model on one device)."""
-
+class DeviceTables(GemmDeviceTables):
     def __init__(self, st: DCCRNStatic, device):
-        f = lambda a: torch.from_numpy(a).to(device)
-        self.wtab, self.btab, self.utab = f(st.wtab), f(st.btab), f(st.utab)
-        self.ktab, self.ntab = f(st.ktab), f(st.ntab)
-        self.tensor_offsets = f(st.layout.tensor_offsets)
-        self.utab_g, self.uperm = gather_ordered_device_tables(st.utab, st.layout.tensor_offsets, f)
-        cfg = st.cfg
-        self.window = f(ops.window_of(cfg.win_type, cfg.win_len))
-        self.wpack = torch.zeros(st.n_wpack, dtype=BF16, device=device)
-        self.bpack = torch.zeros(max(st.n_bpack, 4), dtype=torch.float32, device=device)
+        super().__init__(st, st.layout, device)
+        self.ktab = self.to_device(st.ktab)
+        self.window = self.to_device(ops.window_of(st.cfg.win_type, st.cfg.win_len))
 
 
 class DCCRNWorkspace(GemmWorkspace):
@@ -1069,60 +882,38 @@ class DCCRNWorkspace(GemmWorkspace):
         self._chunk_cache = {}
         self._wg_groups = {}
         # chunk table bound to this workspace's source geometry: [src, (toff<<16)|(fadd&0xffff), element delta, npieces]
-        kt = st.ktab.copy()
+        self.ktab_dev = upload_chunk_table(st.ktab, st.specs.values(), lambda s: [(self.bufs[b].F, self.bufs[b].C) for b, _ in s.srcs],
+                                           self.device)
         for name, s in st.specs.items():
-            bind_chunk_table(st.ktab, kt, s.kt_off, s.K // 8, [(self.bufs[b].F, self.bufs[b].C) for b, _ in s.srcs])
-        self.ktab_dev = torch.from_numpy(kt).to(self.device)
-        for name, s in st.specs.items():
-            d = CGemmDesc()
             tt = T if s.tt == "T" else T + 1
-            for q, (bname, mode) in enumerate(s.srcs):
+            srcs, dsts = [], []
+            for bname, mode in s.srcs:
                 b = self.bufs[bname]
-                d.src[q].ptr = b.ptr
-                d.src[q].T, d.src[q].F, d.src[q].C = b.Tst, b.F, b.C
-                if mode == "drop1":
-                    d.src[q].tlo, d.src[q].thi = 1, T + 1
-                else:
-                    d.src[q].tlo, d.src[q].thi = 0, b.Tst
-            for q, (bname, toff, fmul, fadd) in enumerate(s.dsts):
+                srcs.append((b.ptr, b.Tst, b.F, b.C) + ((1, T + 1) if mode == "drop1" else (0, b.Tst)))
+            for bname, toff, fmul, fadd in s.dsts:
                 b = self.bufs[bname]
-                d.dst[q].ptr = b.ptr
-                d.dst[q].T, d.dst[q].F, d.dst[q].C = b.Tst, b.F, b.C
-                d.dst[q].toff, d.dst[q].fmul, d.dst[q].fadd = toff, fmul, fadd
-                d.dst[q].is_f32 = 1 if b.t.dtype == torch.float32 else 0
-                if s.J == 1:  # dense rows: view the destination as one row per (b,t)
-                    d.dst[q].F, d.dst[q].C = 1, b.F * b.C
-            d.ktab = self.ktab_dev.data_ptr() + 16 * s.kt_off
-            d.ntab = tb.ntab.data_ptr() + 16 * s.nt_off
-            if s.w_off is not None:
-                d.W = tb.wpack.data_ptr() + 2 * s.w_off
-            if s.b_off is not None:
-                d.bias = tb.bpack.data_ptr() + 4 * s.b_off
-            d.M, d.N, d.Npad, d.K = B * tt * s.J, s.N, s.Npad, s.K
-            d.TT, d.J, d.fmul = tt, s.J, s.fmul
+                fc = (1, b.F * b.C) if s.J == 1 else (b.F, b.C)       # dense rows: view the destination as one row per (b,t)
+                dsts.append((b.ptr, b.Tst) + fc + (toff, fmul, fadd, 0, 1 if b.t.dtype == torch.float32 else 0))
+            res = None
+            if s.res is not None:
+                rb, db_ = self.bufs[s.res], self.bufs[s.dsts[0][0]]
+                assert (rb.Tst, rb.F, rb.C) == (db_.Tst, db_.F, db_.C) and rb.t.dtype == torch.bfloat16
+                res = rb.ptr
+            d = fill_desc(srcs, dsts, row_ptr(self.ktab_dev, s.kt_off), row_ptr(tb.ntab, s.nt_off), row_ptr(tb.wpack, s.w_off),
+                          row_ptr(tb.bpack, s.b_off), B * tt * s.J, s.N, s.Npad, s.K, tt, s.J, s.fmul, 0, res)
             d.w_tiled = 1 if s.w_tiled else 0
             if s.stats_of is not None:
                 d.stats = self.bn_stats[s.stats_of].data_ptr()
                 d.stats_cr = s.N // 2
-            if s.res is not None:
-                rb, db_ = self.bufs[s.res], self.bufs[s.dsts[0][0]]
-                assert (rb.Tst, rb.F, rb.C) == (db_.Tst, db_.F, db_.C) and rb.t.dtype == torch.bfloat16
-                d.res = rb.ptr
             if s.conv is not None:
                 d.cv_nf, d.cv_fadd = s.conv[0], s.conv[1]
                 for q in range(2):
                     for kt in range(2):
                         d.cv_toff[q][kt] = s.conv[2][q][kt]
             self.desc[name] = d
-            if s.dw_off is not None:  # weight-gradient twin: dOut replaces the destination
-                w = CGemmDesc.from_buffer_copy(d)
-                w.dW = self.gpack.data_ptr() + 4 * s.dw_off
-                w.dbias = self.gpack.data_ptr() + 4 * s.db_off if s.db_off is not None else None
-                if s.kind == "fwd":
-                    gname = self._grad_buffer_of(s.dsts[0][0])
-                    gb = self.bufs[gname]
-                    w.dst[0].ptr = gb.ptr
-                    w.dst[0].is_f32 = 0
+            if s.dw_off is not None:  # weight-gradient twin: dOut replaces the destination of a forward product
+                w = wgrad_twin(d, row_ptr(self.gpack, s.dw_off), row_ptr(self.gpack, s.db_off),
+                               self.bufs[self._grad_buffer_of(s.dsts[0][0])].ptr if s.kind == "fwd" else None)
                 if name == "enc0.fwd" and self.enc0_bn_in_wgrad:
                     zb, yb, gb = self.bufs["dz0"], self.bufs["y0"], self.bufs["dye0"]
                     assert (zb.Tst, zb.F, zb.C) == (gb.Tst, gb.F, gb.C) == (yb.Tst, yb.F, yb.C) and zb.t.dtype == yb.t.dtype == BF16

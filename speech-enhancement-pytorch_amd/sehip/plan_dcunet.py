@@ -22,8 +22,10 @@ import torch
 
 from . import _lib
 from ._lib import call, ptr, stream, SehipError
-from .workspace import Buf, GemmWorkspace, gather_ordered_device_tables
-from .plan import (Arena, CGemmDesc, GemmSpec, ParamLayout, bind_chunk_table, dense_ntab, enc_entry, npad_of, round_up, BF16)
+from .workspace import Buf, GemmDeviceTables, GemmWorkspace
+from .gemmdesc import (Arena, ParamLayout, UnpackTable, check_unpack_coverage, dense_ntab, enc_entry, fill_desc, npad_of, round_up, row_ptr,
+                       upload_chunk_table, wgrad_twin, BF16)
+from .plan import GemmSpec
 
 
 def stored_channels(c):
@@ -419,53 +421,27 @@ class DCUNetPlan:
 
     def _build_unpack_table(self):
         L, st = self.st.layout, self.st
-        ps, gs, ns = [], [], []
+        ut = UnpackTable(L.n_params)
         done_bias = set()
         for s in self.specs.values():
-            if s.dw_off is None:
-                continue
-            m = s.widx >= 0
-            ps.append(s.widx[m]); ns.append(s.wneg[m])
-            gs.append(s.dw_off + np.flatnonzero(m.reshape(-1)))
-            if s.db_off is not None and s.db_off not in done_bias:
+            if s.dw_off is not None:
+                s.put_unpack(ut, bias=s.db_off not in done_bias)      # (the parity classes of one transposed convolution share it)
                 done_bias.add(s.db_off)
-                for col in (0, 1):
-                    e = s.bias_pairs[:, col].astype(np.int64)
-                    mm = e >= 0
-                    ps.append(e[mm] >> 1); ns.append(e[mm] & 1)
-                    gs.append(s.db_off + np.flatnonzero(mm))
         for pre, tag, cs, cr in self.bn:
             for k, leaf in (("w_re", "bn_re.weight"), ("b_re", "bn_re.bias"), ("w_im", "bn_im.weight"), ("b_im", "bn_im.bias")):
-                ps.append(L.index_array(pre + leaf)); ns.append(np.zeros(cr, np.int64))
-                gs.append(self.bn_g_off[pre][k] + np.arange(cr))
+                ut.put(L.index_array(pre + leaf), self.bn_g_off[pre][k] + np.arange(cr))
         cr_l, cs_l = st.dec_cr[-1], st.dec_c[-1]
-        for k, (leaf, base) in enumerate((("linear.conv_re.weight", 0), ("linear.conv_im.weight", cs_l))):
-            ps.append(L.index_array(leaf).reshape(-1)); ns.append(np.zeros(cr_l, np.int64))
-            gs.append(self.lin_g_off + base + np.arange(cr_l))
+        for leaf, base in (("linear.conv_re.weight", 0), ("linear.conv_im.weight", cs_l)):
+            ut.put(L.index_array(leaf), self.lin_g_off + base + np.arange(cr_l))
         for leaf, pos in (("linear.conv_re.bias", 2 * cs_l), ("linear.conv_im.bias", 2 * cs_l + 1)):
-            ps.append(L.index_array(leaf).reshape(-1)); ns.append(np.zeros(1, np.int64))
-            gs.append(np.asarray([self.lin_g_off + pos]))
-        p = np.concatenate([a.reshape(-1) for a in ps]).astype(np.int64)
-        g = np.concatenate([a.reshape(-1) for a in gs]).astype(np.int64)
-        nn_ = np.concatenate([a.reshape(-1) for a in ns]).astype(np.int64)
-        order = np.argsort(p, kind="stable")
-        p, g, nn_ = p[order], g[order], nn_[order]
-        first = np.searchsorted(p, p, side="left")
-        slot = np.arange(p.shape[0]) - first
-        assert slot.max() < 4, "a parameter feeds more than 4 packed-gradient entries"
-        tab = np.full((L.n_params, 4), -1, dtype=np.int32)
-        tab[p, slot] = ((g << 1) | nn_).astype(np.int32)
-        return tab
+            ut.put(L.index_array(leaf), self.lin_g_off + pos)
+        check_unpack_coverage(L, ut.count, what="DCUnet")
+        return ut.tab
 
 
-class DCUNetDeviceTables:
+class DCUNetDeviceTables(GemmDeviceTables):
     def __init__(self, pl: DCUNetPlan, device):
-        f = lambda a: torch.from_numpy(a).to(device)
-        self.wtab, self.btab, self.utab, self.ntab = f(pl.wtab), f(pl.btab), f(pl.utab), f(pl.ntab)
-        self.tensor_offsets = f(pl.st.layout.tensor_offsets)
-        self.utab_g, self.uperm = gather_ordered_device_tables(pl.utab, pl.st.layout.tensor_offsets, f)
-        self.wpack = torch.zeros(pl.n_wpack, dtype=BF16, device=device)
-        self.bpack = torch.zeros(max(pl.n_bpack, 4), dtype=torch.float32, device=device)
+        super().__init__(pl, pl.st.layout, device)
 
 
 class DCUNetWorkspace(GemmWorkspace):
@@ -529,47 +505,30 @@ class DCUNetWorkspace(GemmWorkspace):
     def _bind(self):
         pl, tb, B = self.pl, self.tb, self.B
         self.desc = {}
-        kt = pl.ktab.copy()
+        self.ktab_dev = upload_chunk_table(pl.ktab, pl.specs.values(), lambda s: [(self.bufs[b].F, self.bufs[b].C) for b, _ in s.srcs],
+                                           self.device)
         for name, s in pl.specs.items():
-            geo = [(self.bufs[b].F, self.bufs[b].C) for b, _ in s.srcs]
-            bind_chunk_table(pl.ktab, kt, s.kt_off, s.K // 8, geo)
-        self.ktab_dev = torch.from_numpy(kt).to(self.device)
-        for name, s in pl.specs.items():
-            d = CGemmDesc()
-            for q, (bname, mode) in enumerate(s.srcs):
-                b = self.bufs[bname]
-                d.src[q].ptr = b.ptr
-                d.src[q].T, d.src[q].F, d.src[q].C = b.Tst, b.F, b.C
-                d.src[q].tlo, d.src[q].thi = 0, b.Tst
+            srcs = [(b.ptr, b.Tst, b.F, b.C, 0, b.Tst) for b in (self.bufs[bname] for bname, _ in s.srcs)]
+            dsts = []
             for q, (bname, toff, fmul, fadd) in enumerate(s.dsts):
                 b = self.bufs[bname]
-                d.dst[q].ptr = b.ptr
-                d.dst[q].T, d.dst[q].F, d.dst[q].C = b.Tst, b.F, b.C
-                d.dst[q].toff, d.dst[q].fmul, d.dst[q].fadd = toff, fmul, fadd
-                d.dst[q].is_f32 = 0
-                d.dst[q].tmul = s.dst_tmul[q]
-            d.ktab = self.ktab_dev.data_ptr() + 16 * s.kt_off
-            d.ntab = tb.ntab.data_ptr() + 16 * s.nt_off
-            d.W = tb.wpack.data_ptr() + 2 * s.w_off if s.w_off is not None else None
+                dsts.append((b.ptr, b.Tst, b.F, b.C, toff, fmul, fadd, s.dst_tmul[q], 0))
+            res = None
+            if s.res is not None:
+                rb, db_ = self.bufs[s.res], self.bufs[s.dsts[0][0]]
+                assert (rb.Tst, rb.F, rb.C) == (db_.Tst, db_.F, db_.C)
+                res = rb.ptr
             # Every convolution here feeds a BatchNorm, which cancels its bias exactly (src/model/dcunet.py:323-338 adds it, :374-386
             # removes it): the products store their output WITHOUT the bias (d.bias stays NULL) and the BatchNorm finalize takes
             # the bias as `shift` (sehip_rbn_finalize_s) for the running mean / the inference mean.  With small-amplitude spectra the
             # bias is ~50x the signal and would otherwise cost the bf16 tensor most of its mantissa (17 % output error measured at
             # 0.1-scale white noise, 1 % without the bias).  (The weight-gradient twin below still sums dOut into the bias gradient.)
-            d.M, d.N, d.Npad, d.K = B * s.tt * s.J, s.N, s.Npad, s.K
-            d.TT, d.J, d.fmul, d.tmul = s.tt, s.J, s.fmul, s.tmul
-            if s.res is not None:
-                rb, db_ = self.bufs[s.res], self.bufs[s.dsts[0][0]]
-                assert (rb.Tst, rb.F, rb.C) == (db_.Tst, db_.F, db_.C)
-                d.res = rb.ptr
+            d = fill_desc(srcs, dsts, row_ptr(self.ktab_dev, s.kt_off), row_ptr(tb.ntab, s.nt_off), row_ptr(tb.wpack, s.w_off), None,
+                          B * s.tt * s.J, s.N, s.Npad, s.K, s.tt, s.J, s.fmul, s.tmul, res)
             if s.kind != "wg":         # (weight-gradient-only products have no forward launch)
                 self.desc[name] = d
             if s.dw_off is not None:   # weight-gradient twin: dOut replaces the destination
-                w = CGemmDesc.from_buffer_copy(d)
-                w.dW = self.gpack.data_ptr() + 4 * s.dw_off
-                w.dbias = self.gpack.data_ptr() + 4 * s.db_off if s.db_off is not None else None
-                out_name = s.dsts[0][0]
-                w.dst[0].ptr = self.bufs["d" + out_name].ptr
+                w = wgrad_twin(d, row_ptr(self.gpack, s.dw_off), row_ptr(self.gpack, s.db_off), self.bufs["d" + s.dsts[0][0]].ptr)
                 if getattr(s, "conv2", None) is not None:
                     w.cv2_nkt, w.cv2_nf, w.cv2_fadd, w.cv2_t0 = s.conv2
                 self.desc[name + ".wg"] = w

@@ -24,7 +24,8 @@ import torch
 
 from . import _lib
 from ._lib import call, ptr, stream, SehipError
-from .plan import Arena, CGemmDesc, ParamLayout, bind_chunk_table, dense_ntab, npad_of, pad_ktab, BF16
+from .gemmdesc import (Arena, CGemmDesc, ParamLayout, UnpackTable, check_unpack_coverage, dense_ntab, fill_desc, npad_of, pad_ktab, row_ptr,
+                       upload_chunk_table, wgrad_twin, BF16)
 from .workspace import Buf, GemmWorkspace
 
 HEADS, NDECAY, MAX_STEPS, GN_EPS = 4, 4, 200, 1e-5
@@ -423,37 +424,14 @@ class DemucsStatic:
     def _build_unpack_table(self):
         L = self.layout
         ia = L.index_array
-        tab = np.full((L.n_params, 4), -1, dtype=np.int32)
-        fill = np.zeros(L.n_params, dtype=np.int8)
-
-        def put(pidx, gidx, unique=False):
-            pidx = np.asarray(pidx, dtype=np.int64).reshape(-1)
-            gidx = np.asarray(gidx, dtype=np.int64).reshape(-1)
-            if pidx.size == 0:
-                return
-            assert gidx.max() < 2 ** 30
-            if unique:                                      # a weight element occurs once in its forward product
-                slot = fill[pidx]
-                assert slot.max() < 4
-                tab[pidx, slot] = (gidx << 1).astype(np.int32)
-                fill[pidx] += 1
-                return
-            order = np.argsort(pidx, kind="stable")        # a parameter may occur several times in one call (the four output
-            ps, gs = pidx[order], gidx[order]               # phases of a transposed convolution share its bias)
-            first = np.flatnonzero(np.r_[True, ps[1:] != ps[:-1]])
-            counts = np.diff(np.r_[first, ps.size])
-            rank = np.arange(ps.size) - np.repeat(first, counts)
-            slot = fill[ps] + rank
-            assert slot.max() < 4
-            tab[ps, slot] = (gs << 1).astype(np.int32)
-            fill[ps[first]] += counts.astype(np.int8)
-
+        ut = UnpackTable(L.n_params)
+        put = ut.put        # (a parameter may occur several times in one call: the four output phases of a transposed convolution share its bias)
         for p in self.prods.values():
             if p.dw_off is None:
                 continue
             w = self.wtab[p.w_off:p.w_off + p.Npad * p.K]
             m = np.flatnonzero(w >= 0)
-            put(w[m] >> 1, p.dw_off + m, unique=True)
+            put(w[m] >> 1, p.dw_off + m)
             if p.db_off is not None:
                 for col in range(p.bias.shape[1]):
                     b = p.bias[:, col]
@@ -466,16 +444,12 @@ class DemucsStatic:
             put(ia(n["gamma"]), n["off"] + np.arange(c)); put(ia(n["beta"]), n["off"] + c + np.arange(c))
             if n["scale"]:
                 put(ia(n["scale"]), n["off"] + 2 * c + np.arange(n["Co"]))
-        used = np.zeros(L.n_params, dtype=bool)
-        for name in L.param_names:
-            off, shape = L.param_off[name]
-            used[off:off + int(np.prod(shape))] = True
-        assert (fill[used] >= 1).all(), "every Demucs parameter has a packed-gradient entry"
+        check_unpack_coverage(L, ut.count, what="Demucs")
         # compact form: one 4-byte entry per parameter + the few parameters with several entries (the biases of the transposed
         # convolutions: one per output phase) as an index list with 16-byte entries
-        self.unpack_entries = fill
-        multi = np.flatnonzero(fill > 1).astype(np.int32)
-        return np.ascontiguousarray(tab[:, 0]), multi, np.ascontiguousarray(tab[multi])
+        self.unpack_entries = ut.count
+        multi = np.flatnonzero(ut.count > 1).astype(np.int32)
+        return np.ascontiguousarray(ut.tab[:, 0]), multi, np.ascontiguousarray(ut.tab[multi])
 
     def _build_pack_runs(self):
         """(base, stride) per 8 packed elements where they are an affine run of parameters, (-1, 0) for 8 padding zeros, otherwise
@@ -587,49 +561,31 @@ class DemucsWorkspace(GemmWorkspace):
     def _bind(self):
         st, tb, B = self.st, self.tb, self.B
         self.desc = {}
-        kt = st.ktab.copy()
-        for p in st.prods.values():
-            bind_chunk_table(st.ktab, kt, p.kt_off, p.K // 8, [(1, self._view(*p.src)[1])])
-        self.ktab_dev = torch.from_numpy(kt).to(self.device)
+        self.ktab_dev = upload_chunk_table(st.ktab, st.prods.values(), lambda p: [(1, self._view(*p.src)[1])], self.device)
         for name, p in st.prods.items():
-            d = CGemmDesc()
-            sb = self.bufs[p.src[0]]
-            sT, sC = self._view(*p.src)
-            d.src[0].ptr, d.src[0].T, d.src[0].F, d.src[0].C, d.src[0].tlo, d.src[0].thi = sb.ptr, sT, 1, sC, 0, sT
-            ob = self.bufs[p.dst[0]]
-            oT, oC = self._view(*p.dst)
-            d.dst[0].ptr, d.dst[0].T, d.dst[0].F, d.dst[0].C = ob.ptr, oT, 1, oC
-            d.dst[0].toff, d.dst[0].fmul, d.dst[0].fadd, d.dst[0].tmul = 0, 1, 0, 1
-            d.dst[0].is_f32 = 1 if ob.t.dtype == torch.float32 else 0
+            sb, ob = self.bufs[p.src[0]], self.bufs[p.dst[0]]
+            (sT, sC), (oT, oC) = self._view(*p.src), self._view(*p.dst)
             tt = (self.Tin if p.tt[0] < 0 else self.lens[p.tt[0]]) + p.tt[1]
             items = B
             if p.framed:
                 nf, tt, _ = self.chunks[p.tt[0]]
                 items = B * nf
             assert tt <= oT, (name, tt, oT)
-            d.ktab = self.ktab_dev.data_ptr() + 16 * p.kt_off
-            d.ntab = tb.ntab.data_ptr() + 16 * p.nt_off
-            d.W = tb.wpack.data_ptr() + 2 * p.w_off
-            if p.b_off is not None:
-                d.bias = tb.bpack.data_ptr() + 4 * p.b_off
-            d.M, d.N, d.Npad, d.K = items * tt, p.N, p.Npad, p.K
-            d.TT, d.J, d.fmul, d.tmul = tt, 1, 1, 1
+            res = None
             if p.res is not None:
                 rb = self.bufs[p.res]
                 assert rb.Tst * rb.C == ob.Tst * ob.C and rb.t.dtype == BF16 and ob.t.dtype == BF16, (name, p.res)
-                d.res = rb.ptr
+                res = rb.ptr
+            d = fill_desc([(sb.ptr, sT, 1, sC, 0, sT)], [(ob.ptr, oT, 1, oC, 0, 1, 0, 1, 1 if ob.t.dtype == torch.float32 else 0)],
+                          row_ptr(self.ktab_dev, p.kt_off), row_ptr(tb.ntab, p.nt_off), row_ptr(tb.wpack, p.w_off), row_ptr(tb.bpack, p.b_off),
+                          items * tt, p.N, p.Npad, p.K, tt, 1, 1, 1, res)
             if not p.wg_only:
                 self.desc[name] = d
             if p.dw_off is not None:
-                w = CGemmDesc.from_buffer_copy(d)
-                w.dW = self.gpack.data_ptr() + 4 * p.dw_off
-                w.dbias = self.gpack.data_ptr() + 4 * p.db_off if p.db_off is not None else None
                 gb = self.bufs[p.dout]
                 assert gb.Tst * gb.C == ob.Tst * ob.C and gb.t.dtype == BF16, (name, p.dout)
-                w.dst[0].ptr = gb.ptr
-                w.dst[0].is_f32 = 0
-                w.res = None
-                self.desc[name + ".wg"] = w
+                w = self.desc[name + ".wg"] = wgrad_twin(d, row_ptr(self.gpack, p.dw_off), row_ptr(self.gpack, p.db_off), gb.ptr)
+                w.res = None             # (the residual belongs to the forward product's epilogue)
         self._bind_dense_wgrads()
 
     def _bind_dense_wgrads(self):

@@ -23,7 +23,7 @@ import torch
 
 from . import _lib
 from ._lib import call, ptr, stream, SehipError
-from .plan import ParamLayout, BF16
+from .gemmdesc import ParamLayout, BF16
 from .plan_rnnmask import (BN_EPS, BN_MOMENTUM, RnnStackWorkspace, pad8, stack_arena, stack_buffer_shapes, stack_pack_launches)
 
 

@@ -21,7 +21,7 @@ import torch
 
 from . import _lib
 from ._lib import call, ptr, stream, SehipError
-from .plan import ParamLayout, BF16
+from .gemmdesc import ParamLayout, BF16
 from .workspace import Workspace
 
 BN_EPS, BN_MOMENTUM = 1e-5, 0.1

@@ -18,8 +18,9 @@ import torch
 
 from . import _lib
 from ._lib import call, ptr, stream, SehipError
-from .plan import Arena, CGemmDesc, GemmSpec, ParamLayout, bind_chunk_table, enc_entry, BF16
-from .workspace import Buf, GemmWorkspace, gather_ordered_device_tables
+from .gemmdesc import Arena, ParamLayout, UnpackTable, check_unpack_coverage, enc_entry, fill_desc, row_ptr, upload_chunk_table, wgrad_twin, BF16
+from .plan import GemmSpec
+from .workspace import Buf, GemmDeviceTables, GemmWorkspace
 
 
 class TasNetConfig:
@@ -155,16 +156,13 @@ class TasNetStatic:
         L, cfg = self.layout, self.cfg
         ia = L.index_array
         N, H, P = cfg.N, cfg.H, cfg.P
-        ps, gs = [], []
+        ut = UnpackTable(L.n_params, limit=1)
         for s in self.specs.values():
-            if s.dw_off is None:
-                continue
-            m = s.widx >= 0
-            ps.append(s.widx[m]); gs.append(s.dw_off + np.flatnonzero(m.reshape(-1)))
+            if s.dw_off is not None:
+                s.put_unpack(ut)
 
         def lin(name, base):
-            idx = ia(name).reshape(-1)
-            ps.append(idx); gs.append(base + np.arange(idx.size))
+            ut.put(ia(name), base + np.arange(ia(name).size))
 
         AL = cfg.audio_channels * cfg.L
         lin("encoder.conv1d_U.weight", self.enc_g_off)
@@ -178,21 +176,13 @@ class TasNetStatic:
             a2, g2, b2 = cfg.inner_names(q)
             lin(g2, o["gch2"]); lin(b2, o["gch2"] + H)
             lin(q + "1.weight", o["a1"]); lin(a2, o["a2"])
-        p = np.concatenate(ps).astype(np.int64)
-        g = np.concatenate(gs).astype(np.int64)
-        assert len(np.unique(p)) == len(p), "every ConvTasNet parameter has exactly one packed-gradient entry"
-        tab = np.full((L.n_params, 4), -1, dtype=np.int32)
-        tab[p, 0] = (g << 1).astype(np.int32)
-        return tab
+        check_unpack_coverage(L, ut.count, exact=True, what="ConvTasNet")
+        return ut.tab
 
 
-class TasNetDeviceTables:
+class TasNetDeviceTables(GemmDeviceTables):
     def __init__(self, st: TasNetStatic, device):
-        f = lambda a: torch.from_numpy(a).to(device)
-        self.wtab, self.utab, self.ntab = f(st.wtab), f(st.utab), f(st.ntab)
-        self.tensor_offsets = f(st.layout.tensor_offsets)
-        self.utab_g, self.uperm = gather_ordered_device_tables(st.utab, st.layout.tensor_offsets, f)
-        self.wpack = torch.zeros(st.n_wpack, dtype=BF16, device=device)
+        super().__init__(st, st.layout, device, bias=False)
 
 
 class TasNetWorkspace(GemmWorkspace):
@@ -238,35 +228,21 @@ class TasNetWorkspace(GemmWorkspace):
     def _bind(self):
         st, tb, M, K = self.st, self.tb, self.M, self.K
         self.desc = {}
-        kt = st.ktab.copy()
+        self.ktab_dev = upload_chunk_table(st.ktab, st.specs.values(), lambda s: [(self.bufs[b].F, self.bufs[b].C) for b, _ in s.srcs],
+                                           self.device)
         for name, s in st.specs.items():
-            bind_chunk_table(st.ktab, kt, s.kt_off, s.K // 8, [(self.bufs[b].F, self.bufs[b].C) for b, _ in s.srcs])
-        self.ktab_dev = torch.from_numpy(kt).to(self.device)
-        for name, s in st.specs.items():
-            d = CGemmDesc()
-            b = self.bufs[s.srcs[0][0]]
-            d.src[0].ptr, d.src[0].T, d.src[0].F, d.src[0].C, d.src[0].tlo, d.src[0].thi = b.ptr, K, 1, b.C, 0, K
-            o = self.bufs[s.dsts[0][0]]
-            d.dst[0].ptr, d.dst[0].T, d.dst[0].F, d.dst[0].C = o.ptr, K, 1, o.C
-            d.dst[0].toff, d.dst[0].fmul, d.dst[0].fadd, d.dst[0].is_f32, d.dst[0].tmul = 0, 1, 0, 0, 1
-            d.ktab = self.ktab_dev.data_ptr() + 16 * s.kt_off
-            d.ntab = tb.ntab.data_ptr() + 16 * s.nt_off
-            d.W = tb.wpack.data_ptr() + 2 * s.w_off
-            d.M, d.N, d.Npad, d.K = M * K, s.N, s.Npad, s.K
-            d.TT, d.J, d.fmul, d.tmul = K, 1, 1, 1
-            if s.res is not None:
-                d.res = self.bufs[s.res].ptr
+            b, o = self.bufs[s.srcs[0][0]], self.bufs[s.dsts[0][0]]
+            d = fill_desc([(b.ptr, K, 1, b.C, 0, K)], [(o.ptr, K, 1, o.C, 0, 1, 0, 1, 0)], row_ptr(self.ktab_dev, s.kt_off),
+                          row_ptr(tb.ntab, s.nt_off), row_ptr(tb.wpack, s.w_off), None, M * K, s.N, s.Npad, s.K, K, 1, 1, 1,
+                          self.bufs[s.res].ptr if s.res is not None else None)
             # (every product here is a 1x1 convolution over dense rows: the library may take the streaming dense-row kernels --
             #  csrc/dgemm.hip forward / input gradient, csrc/wgrad3.hip weight gradient -- where the widths are ones they are built for)
             d.dense_rows = 1 if (b.C == s.K and o.C == s.Npad == s.N) else 0
             self.desc[name] = d
             if s.dw_off is not None:
-                w = CGemmDesc.from_buffer_copy(d)
-                w.dW = self.gpack.data_ptr() + 4 * s.dw_off
-                w.dst[0].ptr = self.bufs[st.dout_of[name]].ptr
-                w.res = None
-                w.dense_rows = 1 if (b.C == s.K and o.C == s.Npad == s.N) else 0     # every product here is a 1x1 convolution over dense rows
-                w.wg_hint = 160          # measured at the C4 shape (ms per step): 96: 4.28, 128: 3.68, 160: 3.59, 192: 3.79, 256: 3.75
+                w = wgrad_twin(d, row_ptr(self.gpack, s.dw_off), None, self.bufs[st.dout_of[name]].ptr)
+                w.res = None             # (the residual belongs to the forward product's epilogue)
+                w.wg_hint = 160         # measured at the C4 shape (ms per step): 96: 4.28, 128: 3.68, 160: 3.59, 192: 3.79, 256: 3.75
                 self.desc[name + ".wg"] = w
         # round 6: the gLN statistics of every block's first 1x1 output inside the product's launch, where the dense-row kernel takes it
         # (sehip_gemm_desc.gln_stats; SEHIP_CTN_NO_FUSED_GLN=1: the separate sehip_ctn_gln_stats pass)

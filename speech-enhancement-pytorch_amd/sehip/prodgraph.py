@@ -10,8 +10,9 @@ buffers of one shape by a workspace.
                      launch groups every step has: prologue (zero, pack), start of a backward pass, join + un-pack
 
 The 1-D Wave-U-Net is the J = 1, F = 1, stride 1 case of the 2-D form.  A plan keeps what is its own: configuration, shape refusals,
-forward() / backward() and the launches around the products.  plan_demucs.py is deliberately not built on this module: its packed-weight
-segments, four-column un-pack, framed rows and dense weight-gradient binding are their own design.
+forward() / backward() and the launches around the products.  The descriptor binder, the un-pack table builder and its coverage proof
+are gemmdesc.py's, shared with the other three plans of the engine.  plan_demucs.py is deliberately not built on this module: its
+packed-weight segments, compact un-pack forms, framed rows and dense weight-gradient binding are their own design.
 """
 import sys
 
@@ -20,7 +21,8 @@ import torch
 
 from . import _lib
 from ._lib import ptr, SehipError
-from .plan import Arena, CGemmDesc, ParamLayout, bind_chunk_table, dense_ntab, enc_entry, npad_of, pad_ktab, BF16
+from .gemmdesc import (Arena, ParamLayout, UnpackTable, check_unpack_coverage, dense_ntab, enc_entry, fill_desc, npad_of, pad_ktab, row_ptr,
+                       upload_chunk_table, wgrad_twin, BF16)
 from .workspace import Buf, GemmWorkspace
 
 
@@ -112,16 +114,8 @@ class ProdStatic:
         extra: [(parameter indices, packed indices)]."""
         Lay = self.layout
         ia = Lay.index_array
-        tab = np.full(Lay.n_params, -1, dtype=np.int32)
-        total = [0]
-
-        def put(pidx, gidx):
-            pidx = np.asarray(pidx, dtype=np.int64).reshape(-1)
-            gidx = np.asarray(gidx, dtype=np.int64).reshape(-1)
-            assert (tab[pidx] < 0).all()
-            tab[pidx] = (gidx << 1).astype(np.int32)
-            total[0] += pidx.size
-
+        ut = UnpackTable(Lay.n_params, limit=1)
+        put = ut.put
         done_bias = set()
         for p in self.prods.values():
             if p.dw_off is None:
@@ -139,14 +133,8 @@ class ProdStatic:
             put(ia(nm["pre"] + "bias"), nm["goff"] + nm["C"] + np.arange(nm["Cr"]))
         for pidx, gidx in extra:
             put(pidx, gidx)
-        used = np.zeros(Lay.n_params, dtype=bool)
-        for name in Lay.param_names:
-            off, shape = Lay.param_off[name]
-            used[off:off + (int(np.prod(shape)) if len(shape) else 1)] = True
-        # as many entries as parameter elements, every element has one, none outside: exactly one each
-        assert total[0] == int(used.sum()) and (tab[used] >= 0).all() and (tab[~used] < 0).all(), \
-            f"every {self.plan_name} parameter has exactly one packed-gradient entry"
-        return tab
+        check_unpack_coverage(Lay, ut.count, exact=True, what=self.plan_name)
+        return np.ascontiguousarray(ut.tab[:, 0])
 
 
 class ProdDeviceTables:
@@ -217,51 +205,39 @@ class ProdWorkspace(GemmWorkspace):
     def _bind(self):
         st, tb = self.st, self.tb
         self.desc = {}
-        kt = st.ktab.copy()
-        for p in st.prods.values():
-            bind_chunk_table(st.ktab, kt, p.kt_off, p.K // 8, [self._src_view(s)[2:] for s in p.srcs])
-        self.ktab_dev = torch.from_numpy(kt).to(self.device)
+        self.ktab_dev = upload_chunk_table(st.ktab, st.prods.values(), lambda p: [self._src_view(s)[2:] for s in p.srcs], self.device)
         for name, p in st.prods.items():
-            d = CGemmDesc()
             tt, jj = self.Tl[p.level], self.Fl[p.level]
-            for q, s in enumerate(p.srcs):
+            srcs, dsts = [], []
+            for s in p.srcs:
                 sp, sT, sF, sC = self._src_view(s)
                 if p.stride == (1, 1):
                     assert (sT, sF) == (tt, jj), (name, s)
                 else:
                     assert sT >= 2 * tt and sF >= 2 * jj, (name, s)
-                d.src[q].ptr, d.src[q].T, d.src[q].F, d.src[q].C, d.src[q].tlo, d.src[q].thi = sp, sT, sF, sC, 0, sT
-            for q, (bname, cols) in enumerate(p.dsts):
+                srcs.append((sp, sT, sF, sC, 0, sT))
+            for bname, cols in p.dsts:
                 ob = self.bufs[bname]
                 assert ob.C == cols, (name, bname)
-                d.dst[q].ptr, d.dst[q].T, d.dst[q].F, d.dst[q].C, d.dst[q].is_f32 = ob.ptr, ob.Tst, ob.F, ob.C, 0
                 if p.scatter is None:
                     assert (ob.Tst, ob.F) == (tt, jj), (name, bname)
-                    d.dst[q].toff, d.dst[q].fmul, d.dst[q].fadd, d.dst[q].tmul = 0, 1, 0, 1
+                    dsts.append((ob.ptr, ob.Tst, ob.F, ob.C, 0, 1, 0, 1, 0))
                 else:
                     assert ob.Tst >= 2 * tt and ob.F >= 2 * jj, (name, bname)
-                    d.dst[q].toff, d.dst[q].fmul, d.dst[q].fadd, d.dst[q].tmul = p.scatter[0], 2, p.scatter[1], 2
-            d.ktab = self.ktab_dev.data_ptr() + 16 * p.kt_off
-            d.ntab = tb.ntab.data_ptr() + 16 * p.nt_off
-            d.W = tb.wpack.data_ptr() + 2 * p.w_off
-            if p.b_off is not None:
-                d.bias = tb.bpack.data_ptr() + 4 * p.b_off
-            d.M, d.N, d.Npad, d.K = self.items * tt * jj, p.N, p.Npad, p.K
-            d.TT, d.J, d.tmul, d.fmul = tt, jj, p.stride[0], p.stride[1]
+                    dsts.append((ob.ptr, ob.Tst, ob.F, ob.C, p.scatter[0], 2, p.scatter[1], 2, 0))
+            ob = self.bufs[p.dsts[0][0]]
+            res = None
             if p.res is not None:
-                rb, ob = self.bufs[p.res], self.bufs[p.dsts[0][0]]
+                rb = self.bufs[p.res]
                 assert (rb.Tst, rb.F, rb.C) == (ob.Tst, ob.F, ob.C), (name, p.res)
-                d.res = rb.ptr
-            self.desc[name] = d
+                res = rb.ptr
+            d = self.desc[name] = fill_desc(srcs, dsts, row_ptr(self.ktab_dev, p.kt_off), row_ptr(tb.ntab, p.nt_off),
+                                            row_ptr(tb.wpack, p.w_off), row_ptr(tb.bpack, p.b_off), self.items * tt * jj, p.N, p.Npad,
+                                            p.K, tt, jj, p.stride[1], p.stride[0], res)
             if p.dw_off is not None:
-                w = CGemmDesc.from_buffer_copy(d)
-                w.dW = self.gpack.data_ptr() + 4 * p.dw_off
-                if p.db_off is not None:
-                    w.dbias = self.gpack.data_ptr() + 4 * p.db_off
-                gb, ob = self.bufs[p.dout], self.bufs[p.dsts[0][0]]
+                gb = self.bufs[p.dout]
                 assert (gb.Tst, gb.F, gb.C) == (ob.Tst, ob.F, ob.C), (name, p.dout)
-                w.dst[0].ptr = gb.ptr
-                self.desc[name + ".wg"] = w
+                self.desc[name + ".wg"] = wgrad_twin(d, row_ptr(self.gpack, p.dw_off), row_ptr(self.gpack, p.db_off), gb.ptr)
 
     # ---- launches (gemm, wgrad: GemmWorkspace) ------------------------------------------------------------------------
     def _launch(self, name, *a):

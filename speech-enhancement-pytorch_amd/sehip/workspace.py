@@ -1,6 +1,7 @@
 """What every plan's workspace shares: the life cycle the models' workspace cache relies on (generation / pinned / closed), and for the
 plans built on the implicit-GEMM engine the event pool, the product launches, the weight gradients on the side stream and the un-pack of
-the packed gradients.  What a plan allocates, binds and launches in forward() / backward() stays in its own module.
+the packed gradients.  What a plan allocates, binds and launches in forward() / backward() stays in its own module; the descriptor type, its binder and the
+un-pack table builder are gemmdesc.py's.  GemmDeviceTables: the device copies of the tables of the plans with a four-column un-pack.
 """
 import ctypes as C
 import os
@@ -10,6 +11,7 @@ import torch
 
 from . import _lib
 from ._lib import call, ptr, stream, SehipError
+from .gemmdesc import BF16
 
 
 class Buf:
@@ -46,6 +48,21 @@ def gather_ordered_device_tables(utab, tensor_offsets, to_device):
         return None, None
     tg, pm = gather_ordered_unpack_table(utab, tensor_offsets)
     return to_device(tg), to_device(pm)
+
+
+class GemmDeviceTables:
+    """Device copies of the static tables of a plan with the four-column un-pack table (shared by every workspace of a model on one
+    device) and its packed weights; bias=True: the bias table and the packed biases too.  A subclass adds what else its plan reads."""
+
+    def __init__(self, st, layout, device, bias=True):
+        f = self.to_device = lambda a: torch.from_numpy(a).to(device)
+        self.wtab, self.utab, self.ntab = f(st.wtab), f(st.utab), f(st.ntab)
+        self.tensor_offsets = f(layout.tensor_offsets)
+        self.utab_g, self.uperm = gather_ordered_device_tables(st.utab, layout.tensor_offsets, f)
+        self.wpack = torch.zeros(st.n_wpack, dtype=BF16, device=device)
+        if bias:
+            self.btab = f(st.btab)
+            self.bpack = torch.zeros(max(st.n_bpack, 4), dtype=torch.float32, device=device)
 
 
 class Workspace:
