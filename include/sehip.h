@@ -600,6 +600,35 @@ int sehip_ctns_dwconv(const void* h1, void* hist, const int* phase, const int* p
 int sehip_ctns_decoder(const float* w, const void* mask_bf16, const float* V, float* tail, const int* phase, const int* pos, int S, int Kc,
                        int N, int L, int ac, int Cs, float* out, void* stream);
 int sehip_ctns_advance(int* pos, int* phase, int S, int Kc, void* stream);
+/* ---- DCCRN chunk by chunk (csrc/dccrn_stream.hip; sehip/model/dccrn_stream.py): S streams, Kc hops (Kc win_inc samples per stream) per
+ * call; win_len a multiple of win_inc, R = win_len / win_inc.  pos [S] int32: index of the first frame of the coming call (0 on a fresh
+ * stream); end [S] int32: number of frames of the clip, INT_MAX while the stream is open -- a frame >= end is absent (a zero row for
+ * every decoder product, nothing in the overlap-add).  Decoder j lags the encoder by j + 1 frames, the mask by 6, the output by
+ * 6 + R - 1 hops.  Carried state that a launch renews exists twice; phase [1] int32 names the current half (read phase, write phase ^ 1).
+ *      analysis  : x fp32 [S][Kc hop], carry fp32 [2][S][win - hop] -> spec fp32 [S][Kc][257][2] (sehip_stft_fwd's arithmetic), the
+ *                  last 6 rows of ring | spec into the other half of ring fp32 [2][S][6][257][2], enc bf16 [S][1 + Kc][256][2] (row 0:
+ *                  the current half of enc_hist bf16 [2][S][256][2]), the other halves of enc_hist and carry
+ *      norm_hist : y bf16 [S][Kc][F][2 Cr] -> z bf16 [S][H + Kc][F][2 Cr]: rows 0 .. H - 1 the current half of hist bf16
+ *                  [2][S][H][F][2 Cr], then the chunk rows through the coefficient records of sehip_cbn_finalize and PReLU (a row's
+ *                  arithmetic is sehip_cbn_apply's; coef == NULL: copied), row k a zero row when pos + k - lag >= end; the last H rows
+ *                  of z into the other half of hist
+ *      lstm_carry: step Kc of the h bf16 [4][S][Kc + 1][H] / c fp32 [4][ceil(S/4) 4][Kc + 1][H] records of sehip_lstm_fwd_chunk
+ *                  (run with T = Kc + 1 over [1, Kc + 1)) -> step 0
+ *      synthesis : frames pos - 6 + k, k < Kc: spectrum row k of (current half of ring | spec), mask fp32 [S][Kc][256][2], masking mode,
+ *                  inverse transform and window (sehip_istft_fwd's arithmetic) into frames_ws fp32 [S][Kc][win]; out fp32 [S][Kc hop]:
+ *                  every sample stored once = (carried tail + the chunk's frames in ascending order) * inv_coff [hop], clamped, exact
+ *                  zeros for hop blocks with a negative index; the other half of tail fp32 [2][S][win - hop].  No atomics.
+ *      mark_end  : end[s] = pos[s] + extra            advance : pos[s] += Kc, phase ^= 1 */
+int sehip_dcs_analysis(const float* x, float* carry, const int* phase, const float* window, int S, int Kc, int win, int hop, float* spec,
+                       float* ring, void* enc_bf16, void* enc_hist_bf16, void* stream);
+int sehip_dcs_norm_hist(const void* y, const float* coef, const float* slope, void* hist, const int* phase, const int* pos, const int* end,
+                        int lag, int S, int Kc, int H, int F, int Cr, void* z, void* stream);
+int sehip_dcs_lstm_carry(void* h_bf16, float* c, int S, int Kc, int hidden, void* stream);
+int sehip_dcs_synthesis(const float* spec, const float* ring, const float* mask, const float* window, const float* inv_coff, float* tail,
+                        const int* phase, const int* pos, const int* end, int S, int Kc, int win, int hop, int mode, float* frames_ws,
+                        float* out, void* stream);
+int sehip_dcs_mark_end(const int* pos, int* end, int S, int extra, void* stream);
+int sehip_dcs_advance(int* pos, int* phase, int S, int Kc, void* stream);
 /* mask_nonlinear='softmax' (src/model/conv_tasnet.py:298-299: F.softmax(score, dim=1) over the Cs <= 8 sources): score / out bf16
  * [rows = M * K][Cs][N].  The decoder entry points below take `out` as their mask logits (their relu is the identity on it); what
  * sehip_ctn_decoder_bwd writes for it is the gradient of the mask, which sehip_ctn_mask_softmax_bwd turns into the gradient of the

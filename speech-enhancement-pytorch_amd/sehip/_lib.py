@@ -155,6 +155,12 @@ _PROTOS = {
     "sehip_ctns_dwconv": [P, P, P, P, P, P, P, P, I, I, I, I, I, P, P],
     "sehip_ctns_decoder": [P, P, P, P, P, P, I, I, I, I, I, I, P, P],
     "sehip_ctns_advance": [P, P, I, I, P],
+    "sehip_dcs_analysis": [P, P, P, P, I, I, I, I, P, P, P, P, P],
+    "sehip_dcs_norm_hist": [P, P, P, P, P, P, P, I, I, I, I, I, I, P, P],
+    "sehip_dcs_lstm_carry": [P, P, I, I, I, P],
+    "sehip_dcs_synthesis": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, P, P, P],
+    "sehip_dcs_mark_end": [P, P, I, I, P],
+    "sehip_dcs_advance": [P, P, I, I, P],
     "sehip_dmx_prep": [P, I, I, I, I, I, I, I, I, P, I, I, P, P, P, P],
     "sehip_dmx_post": [P, P, I, I, I, L, I, I, I, P, I, I, P, P],
     "sehip_dmx_post_bwd": [P, P, I, I, I, L, I, I, I, P, I, I, P, P],
