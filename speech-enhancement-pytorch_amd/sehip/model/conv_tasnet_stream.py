@@ -21,14 +21,15 @@ phantom built from the zero carry that contributes nothing).
 
 A chunk is ONE chain of 4 R X + 5 launches (+ 1 with the softmax mask) on the current stream: encoder, bottleneck product, per block
 {product, depthwise step, cLN, product with the residual}, mask product, decoder, counter.  No side stream, no allocation, no
-readback.  graph=True captures that chain once (torch.cuda.graph) and feed() copies into a static input and replays.
+readback.  Construction, feed(), the capture of that chain under graph=True and reset() are streamer.ChunkStreamer's.
 """
 import ctypes as C
 
 import torch
 
-from .._lib import SehipError, call, ptr, stream, stream_scope
+from .._lib import SehipError, call, ptr, stream
 from ..gemmdesc import BF16, fill_desc, row_ptr, upload_chunk_table
+from . import streamer
 from .conv_tasnet import ConvTasNet
 
 
@@ -42,47 +43,25 @@ def state_bytes_of(cfg, streams):
 
 def check_feed_input(x, streams, audio_channels, samples, device):
     """feed()'s argument check (before any launch): x [streams, audio_channels, samples] fp32 on `device`."""
-    if not isinstance(x, torch.Tensor):
-        raise SehipError(f"ConvTasNetStreamer.feed: x must be a tensor, got {type(x).__name__}")
-    want = (streams, audio_channels, samples)
-    if tuple(x.shape) != want:
-        raise SehipError(f"ConvTasNetStreamer.feed: x must have shape [streams, audio_channels, chunk_frames * L/2] = {list(want)}, "
-                         f"got {list(x.shape)}")
-    if x.dtype != torch.float32:
-        raise SehipError(f"ConvTasNetStreamer.feed: x must have dtype torch.float32, got {x.dtype}")
-    if x.device != device:
-        raise SehipError(f"ConvTasNetStreamer.feed: x must be on device {device} (the model's), got {x.device}")
+    streamer.check_feed_input("ConvTasNetStreamer", x, (streams, audio_channels, samples), ConvTasNetStreamer.SHAPE_WORDS, device)
 
 
-class ConvTasNetStreamer:
-    def __init__(self, model, streams=1, chunk_frames=1, graph=False):
-        if not isinstance(model, ConvTasNet):
-            raise SehipError(f"ConvTasNetStreamer: model must be a sehip.model.ConvTasNet, got {type(model).__name__}")
-        cfg = model.cfg
+class ConvTasNetStreamer(streamer.ChunkStreamer):
+    MODEL = ConvTasNet
+    SHAPE_WORDS = "[streams, audio_channels, chunk_frames * L/2]"
+
+    @staticmethod
+    def _check_cfg(cfg):
         if not cfg.causal:
             raise SehipError("ConvTasNetStreamer: model was built with causal=False: its depthwise convolutions read future frames, "
                              "only causal=True, norm_type='cLN' can run chunk by chunk")
         if cfg.norm_type != "cLN":
             raise SehipError(f"ConvTasNetStreamer: model was built with norm_type={cfg.norm_type!r}: gLN's statistics span the whole clip, "
                              "so no frame is final before the clip ends; only causal=True, norm_type='cLN' can run chunk by chunk")
-        if not isinstance(streams, int) or streams < 1:
-            raise SehipError(f"ConvTasNetStreamer: streams={streams!r} must be an integer >= 1")
-        if not isinstance(chunk_frames, int) or chunk_frames < 1:
-            raise SehipError(f"ConvTasNetStreamer: chunk_frames={chunk_frames!r} must be an integer >= 1")
-        dev = model.flat_params.device
-        if dev.type != "cuda":
-            raise SehipError(f"ConvTasNetStreamer: model is on {dev}: the HIP path needs a gfx950 GPU (no CPU fallback); "
-                             "call model.to('cuda') first")
-        self.model, self.cfg, self.st, self.device = model, cfg, model.static, dev
-        self.streams, self.chunk_frames, self.graph = streams, chunk_frames, bool(graph)
-        self.delay = cfg.L // 2
-        self.chunk_samples = chunk_frames * self.delay
-        self.state_bytes = state_bytes_of(cfg, streams)
-        self._alloc()
-        self._bind()
-        self._graph = None
-        self._epoch = None
-        self._sync_model()
+
+    def _sizes(self):
+        h = self.cfg.L // 2
+        return h, self.chunk_frames * h, state_bytes_of(self.cfg, self.streams)
 
     # ---- buffers and descriptors ---------------------------------------------------------------------
     def _alloc(self):
@@ -95,7 +74,6 @@ class ConvTasNetStreamer:
         self.carry = z(2, S, ac, h)
         self.hist = [z(2, S, (cfg.P - 1) * 2 ** x, H, dtype=BF16) for _, x in self.st.blocks]
         self.tail = z(2, S, Cs, ac, h)
-        self._calls = 0          # host mirror of `phase`: flush() reads the current half of the tail
         # work buffers of one chunk: the residual stream alternates between two buffers, h1 / h2 / u are shared by all blocks
         self.xin = z(S, ac, Kc * h)
         self.w = z(S, Kc, N)
@@ -108,6 +86,9 @@ class ConvTasNetStreamer:
         f = lambda a: torch.from_numpy(a).to(dev)
         self.wtab, self.ntab = f(self.st.wtab), f(self.st.ntab)
         self.wpack = z(self.st.n_wpack, dtype=BF16)
+
+    def _state_tensors(self):
+        return [self.pos, self.phase, self.carry, self.tail] + self.hist
 
     def _buf(self, name):
         """activation buffer behind a buffer name of the plan's forward specs"""
@@ -144,18 +125,10 @@ class ConvTasNetStreamer:
         self.model._require_gpu()
         call("sehip_pack_bf16", ptr(self.model.flat_params), ptr(self.wtab), self.st.n_wpack, ptr(self.wpack), stream())
 
-    def _sync_model(self):
-        if self._epoch != self.model.storage_epoch:
-            if self.model.flat_params.device != self.device:
-                raise SehipError(f"ConvTasNetStreamer: model moved from {self.device} to {self.model.flat_params.device}; build a new streamer")
-            self.refresh_weights()
-            self._graph = None          # (captured launches hold pointers into the old flat parameters)
-            self._epoch = self.model.storage_epoch
-
     # ---- one chunk -----------------------------------------------------------------------------------
     def _chunk(self):
         """xin -> out, state advanced: the chain of launches on the current stream"""
-        st, cfg, a = self.st, self.cfg, self.act
+        st, cfg, a, call = self.st, self.cfg, self.act, self._call
         S, Kc, N, H = self.streams, self.chunk_frames, cfg.N, cfg.H
         params, off = self.model.flat_params, self.st.layout.param_off
         pp = lambda n: params.data_ptr() + 4 * off[n][0]
@@ -182,52 +155,16 @@ class ConvTasNetStreamer:
              cfg.audio_channels, cfg.C, ptr(self.out), stream())
         call("sehip_ctns_advance", pos, ph, S, Kc, stream())
 
-    def _capture(self):
-        call("sehip_init")
-        torch.cuda.synchronize(self.device)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g), stream_scope():          # (records, runs nothing: the state does not move; the scope: the capturing stream)
-            self._chunk()
-        return g
-
-    def feed(self, x):
-        """x [S, ac, Kc * L/2] fp32 on the model's device -> [S, C, ac, Kc * L/2]: the offline output of the samples fed so far, delayed
-        by L/2 samples."""
-        check_feed_input(x, self.streams, self.cfg.audio_channels, self.chunk_samples, self.device)
-        with torch.no_grad(), stream_scope():
-            self._sync_model()
-            self.xin.copy_(x)
-            if self.graph:
-                if self._graph is None:
-                    self._graph = self._capture()
-                self._graph.replay()
-            else:
-                self._chunk()
-            self._calls += 1
-            return self.out.clone()
-
     def flush(self):
         """The last L/2 samples of every stream [S, C, ac, L/2] (the carried tail: no compute); then all streams are reset."""
         with torch.no_grad():
-            t = self.tail[self._calls & 1].clone()
+            t = self.tail[self.chunks & 1].clone()
             self.reset()
             return t
 
-    def reset(self, which=None):
-        """Starts a new call on all streams (which=None) or on those of an index list / bool mask [S]: pos = -1, both carries zero.  The
-        other streams are untouched.  (The depthwise history needs no clearing: all of its rows have negative frame indices then.)"""
-        with torch.no_grad():
-            if which is None:
-                idx = slice(None)
-            else:
-                idx = torch.as_tensor(which, device=self.device)
-                if idx.dtype == torch.bool:
-                    if tuple(idx.shape) != (self.streams,):
-                        raise SehipError(f"ConvTasNetStreamer.reset: which as a bool mask must have shape [{self.streams}], got {list(idx.shape)}")
-                else:
-                    idx = idx.reshape(-1).long()
-                    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= self.streams):
-                        raise SehipError(f"ConvTasNetStreamer.reset: which holds a stream index outside [0, {self.streams})")
-            self.pos[idx] = -1
-            self.carry[:, idx] = 0
-            self.tail[:, idx] = 0
+    def _clear(self, idx):
+        """A new call on the streams idx: pos = -1, both carries zero.  (The depthwise history needs no clearing: all of its rows have
+        negative frame indices then.)"""
+        self.pos[idx] = -1
+        self.carry[:, idx] = 0
+        self.tail[:, idx] = 0

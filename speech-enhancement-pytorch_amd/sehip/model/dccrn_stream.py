@@ -27,7 +27,7 @@ product, nothing in the overlap-add), which feeding zeros alone does not reprodu
 
 A chunk is ONE chain of launches on the current stream (analysis; per encoder layer product + normalise; per LSTM layer two input
 products + the recurrence + its state carry; two projections + history; per decoder layer two products (+ normalise); synthesis (two
-launches); advance) with the same arguments every time: graph=True captures it once (torch.cuda.graph) and feed() replays it.
+launches); advance) with the same arguments every time.  Construction, feed(), the capture under graph=True and reset() are ChunkStreamer's.
 """
 import ctypes as C
 
@@ -37,6 +37,7 @@ import torch
 from .. import ops
 from .._lib import SehipError, call, ptr, stream, stream_scope
 from ..gemmdesc import BF16, Arena, enc_entry, fill_desc, row_ptr, upload_chunk_table
+from . import streamer
 from .dccrn import DCCRN
 
 LA = 6                       # frames of look-ahead: one per decoder layer
@@ -66,56 +67,28 @@ def state_bytes_of(cfg, streams):
     return streams * per + 4
 
 
-def check_model(model, streams=1, chunk_frames=1):
-    """The constructor's refusals (before any launch)."""
-    if not isinstance(model, DCCRN):
-        raise SehipError(f"DCCRNStreamer: model must be a sehip.model.DCCRN, got {type(model).__name__}")
-    cfg = model.cfg
-    if not cfg.use_clstm:
-        raise SehipError("DCCRNStreamer: model was built with use_clstm=False: the carried-state recurrence is built for the complex "
-                         "LSTM only")
-    if cfg.win_len % cfg.win_inc != 0:
-        raise SehipError(f"DCCRNStreamer: win_len={cfg.win_len} is not a multiple of win_inc={cfg.win_inc}: the delay "
-                         "(6 + win_len / win_inc - 1) * win_inc needs an integer number of hops per window")
-    if not isinstance(streams, int) or isinstance(streams, bool) or streams < 1:
-        raise SehipError(f"DCCRNStreamer: streams={streams!r} must be an integer >= 1")
-    if not isinstance(chunk_frames, int) or isinstance(chunk_frames, bool) or chunk_frames < 1:
-        raise SehipError(f"DCCRNStreamer: chunk_frames={chunk_frames!r} must be an integer >= 1")
-    dev = model.flat_params.device
-    if dev.type != "cuda":
-        raise SehipError(f"DCCRNStreamer: model is on {dev}: the HIP path needs a gfx950 GPU (no CPU fallback); call model.to('cuda') first")
-    return dev
-
-
 def check_feed_input(x, streams, samples, device):
     """feed()'s argument check (before any launch): x [streams, 1, samples] fp32 on `device`."""
-    if not isinstance(x, torch.Tensor):
-        raise SehipError(f"DCCRNStreamer.feed: x must be a tensor, got {type(x).__name__}")
-    want = (streams, 1, samples)
-    if tuple(x.shape) != want:
-        raise SehipError(f"DCCRNStreamer.feed: x must have shape [streams, 1, chunk_frames * win_inc] = {list(want)}, got {list(x.shape)}")
-    if x.dtype != torch.float32:
-        raise SehipError(f"DCCRNStreamer.feed: x must have dtype torch.float32, got {x.dtype}")
-    if x.device != device:
-        raise SehipError(f"DCCRNStreamer.feed: x must be on device {device} (the model's), got {x.device}")
+    streamer.check_feed_input("DCCRNStreamer", x, (streams, 1, samples), DCCRNStreamer.SHAPE_WORDS, device)
 
 
-class DCCRNStreamer:
-    def __init__(self, model, streams=1, chunk_frames=1, graph=False):
-        dev = check_model(model, streams, chunk_frames)
-        cfg = model.cfg
-        self.model, self.cfg, self.st, self.device = model, cfg, model.static, dev
-        self.streams, self.chunk_frames, self.graph = streams, chunk_frames, bool(graph)
-        self.delay = delay_of(cfg.win_len, cfg.win_inc)
-        self.chunk_samples = chunk_frames * cfg.win_inc
-        self.state_bytes = state_bytes_of(cfg, streams)
-        self.launches = 0            # launches of one chunk (counted when the chain first runs or is captured)
-        self._tables()
-        self._alloc()
-        self._bind()
-        self._graph = None
-        self._epoch = None
-        self._sync_model()
+class DCCRNStreamer(streamer.ChunkStreamer):
+    MODEL = DCCRN
+    SHAPE_WORDS = "[streams, 1, chunk_frames * win_inc]"
+    UNCOUNTED_LAUNCHES = 1           # (the synthesis is two launches)
+
+    @staticmethod
+    def _check_cfg(cfg):
+        if not cfg.use_clstm:
+            raise SehipError("DCCRNStreamer: model was built with use_clstm=False: the carried-state recurrence is built for the complex "
+                             "LSTM only")
+        if cfg.win_len % cfg.win_inc != 0:
+            raise SehipError(f"DCCRNStreamer: win_len={cfg.win_len} is not a multiple of win_inc={cfg.win_inc}: the delay "
+                             "(6 + win_len / win_inc - 1) * win_inc needs an integer number of hops per window")
+
+    def _sizes(self):
+        cfg = self.cfg
+        return delay_of(cfg.win_len, cfg.win_inc), self.chunk_frames * cfg.win_inc, state_bytes_of(cfg, self.streams)
 
     # ---- product names -------------------------------------------------------------------------------
     def _names(self):
@@ -172,7 +145,7 @@ class DCCRNStreamer:
         self.h = {l: bz(4, S, Kc + 1, hid) for l in range(1, L + 1)}
         self.c = {l: z(4, Sp, Kc + 1, hid) for l in range(1, L + 1)}
         # work buffers of one chunk
-        self.xin = z(S, Kc * cfg.win_inc)
+        self.xin = z(S, 1, Kc * cfg.win_inc)
         self.spec = z(S, Kc, 257, 2)
         self.enc_in = bz(S, 1 + Kc, 256, 2)
         self.y = {n: bz(S, Kc, F, Cc) for n, (H, F, Cc) in self.geo.items()}              # a product's chunk rows
@@ -181,7 +154,7 @@ class DCCRNStreamer:
         self.gates = bz(4, Sp, Kc + 1, 4 * hid)       # (records of sehip_lstm_fwd_chunk that nobody reads here: shared by the layers)
         self.mask = z(S, Kc, 256, 2)
         self.frames = z(S, Kc, cfg.win_len)
-        self.out = z(S, Kc * cfg.win_inc)
+        self.out = z(S, 1, Kc * cfg.win_inc)
         # eval-mode BatchNorm records (sehip_cbn_finalize, training = 0), one per layer with a BatchNorm
         self.bn_coef = {pre: z(cr, 16) for pre, cr in self.st.bn}
         maxcr = max(cr for _, cr in self.st.bn)
@@ -289,24 +262,15 @@ class DCCRNStreamer:
             call("sehip_cbn_finalize", ptr(self.bn_part), pp("1.Wrr"), pp("1.Wri"), pp("1.Wii"), pp("1.Br"), pp("1.Bi"), bp("1.RMr"),
                  bp("1.RMi"), bp("1.RVrr"), bp("1.RVri"), bp("1.RVii"), None, 1, cr, eps, 0.1, 0, ptr(self.bn_coef[pre]), stream())
 
-    def _sync_model(self):
-        if self._epoch != self.model.storage_epoch:
-            if self.model.flat_params.device != self.device:
-                raise SehipError(f"DCCRNStreamer: model moved from {self.device} to {self.model.flat_params.device}; build a new streamer")
-            self.refresh_weights()
-            self._graph = None          # (captured launches hold pointers into the old flat parameters)
-            self._epoch = self.model.storage_epoch
-
     # ---- one chunk -----------------------------------------------------------------------------------
     def _chunk(self):
         """xin -> out, state advanced: the chain of launches on the current stream"""
-        cfg, S, Kc = self.cfg, self.streams, self.chunk_frames
-        L, hid, n = cfg.rnn_layers, cfg.hid, [0]
+        cfg, S, Kc, call = self.cfg, self.streams, self.chunk_frames, self._call
+        L, hid = cfg.rnn_layers, cfg.hid
         params, off = self.model.flat_params, self.st.layout.param_off
         ph, pos, end = ptr(self.phase), ptr(self.pos), ptr(self.end)
 
         def run(name, *args):
-            n[0] += 1
             call(name, *args, stream())
 
         def gemm(name):
@@ -342,43 +306,6 @@ class DCCRNStreamer:
         run("sehip_dcs_synthesis", ptr(self.spec), ptr(self.ring), ptr(self.mask), ptr(self.window), ptr(self.inv_coff), ptr(self.tail), ph,
             pos, end, S, Kc, cfg.win_len, cfg.win_inc, self.mode, ptr(self.frames), ptr(self.out))
         run("sehip_dcs_advance", pos, ph, S, Kc)
-        self.launches = n[0] + 1         # (the synthesis is two launches)
-
-    def _capture(self):
-        """Captures one chunk.  The chain runs once eagerly first, on the capturing stream, with the state saved and put back: the engine
-        sizes its per-stream scratch (split-K partial sums) on a product's first launch, which must not happen inside a capture."""
-        call("sehip_init")
-        torch.cuda.synchronize(self.device)
-        side = torch.cuda.Stream(device=self.device)
-        saved = [t.clone() for t in self._state_tensors()]
-        with torch.cuda.stream(side), stream_scope():
-            self._chunk()
-        side.synchronize()
-        for t, v in zip(self._state_tensors(), saved):
-            t.copy_(v)
-        torch.cuda.synchronize(self.device)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=side), stream_scope():     # (records, runs nothing: the state does not move)
-            self._chunk()
-        return g
-
-    def _run(self, x):
-        self.xin.copy_(x.reshape(self.streams, -1))
-        if self.graph:
-            if self._graph is None:
-                self._graph = self._capture()
-            self._graph.replay()
-        else:
-            self._chunk()
-        return self.out.view(self.streams, 1, -1).clone()
-
-    def feed(self, x):
-        """x [S, 1, Kc * win_inc] fp32 on the model's device -> [S, 1, Kc * win_inc]: the offline output of the samples fed so far,
-        delayed by `delay` samples."""
-        check_feed_input(x, self.streams, self.chunk_samples, self.device)
-        with torch.no_grad(), stream_scope():
-            self._sync_model()
-            return self._run(x)
 
     def flush(self):
         """The last `delay` samples of every stream [S, 1, D]: end[s] = pos[s] + R - 1 is marked, then LA + R - 1 hops of zeros are fed
@@ -394,29 +321,18 @@ class DCCRNStreamer:
             self.reset()
             return t
 
-    def reset(self, which=None):
-        """Starts a new clip on all streams (which=None) or on those of an index list / bool mask [S]: pos = 0, end open, every carried
-        piece zero (both halves).  The other streams are untouched."""
-        with torch.no_grad():
-            if which is None:
-                idx = torch.arange(self.streams, device=self.device)
-            else:
-                idx = torch.as_tensor(which, device=self.device)
-                if idx.dtype == torch.bool:
-                    if tuple(idx.shape) != (self.streams,):
-                        raise SehipError(f"DCCRNStreamer.reset: which as a bool mask must have shape [{self.streams}], got {list(idx.shape)}")
-                    idx = idx.nonzero().reshape(-1)
-                else:
-                    idx = idx.reshape(-1).long()
-                    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= self.streams):
-                        raise SehipError(f"DCCRNStreamer.reset: which holds a stream index outside [0, {self.streams})")
-            self.pos[idx] = 0
-            self.end[idx] = NO_END
-            for t in [self.carry, self.tail, self.ring, self.enc_hist] + list(self.hist.values()):
-                t[:, idx] = 0
-            hid = self.cfg.hid
-            for l in self.h:
-                self.h[l][:, idx, 0] = 0
-                # the cell-state record of a step is [batch tile][thread]; thread = 64 w + 16 ug + 4 rs + (stream mod 4) (csrc/lstm.hip)
-                cv = self.c[l].view(4, -1, self.chunk_frames + 1, hid // 16, 4, 4, 4)
-                cv[:, idx // 4, 0, :, :, :, idx % 4] = 0
+    def _clear(self, idx):
+        """A new clip on the streams idx: pos = 0, end open, every carried piece zero (both halves)."""
+        self.pos[idx] = 0
+        self.end[idx] = NO_END
+        for t in [self.carry, self.tail, self.ring, self.enc_hist] + list(self.hist.values()):
+            t[:, idx] = 0
+        hid = self.cfg.hid
+        for l in self.h:
+            self.h[l][:, idx, 0] = 0
+            # the cell-state record of a step is [batch tile][thread]; thread = 64 w + 16 ug + 4 rs + (stream mod 4) (csrc/lstm.hip)
+            cv = self.c[l].view(4, -1, self.chunk_frames + 1, hid // 16, 4, 4, 4)
+            cv[:, idx // 4, 0, :, :, :, idx % 4] = 0
+
+
+check_model = DCCRNStreamer.check_args          # the constructor's refusals (before any launch)

@@ -97,6 +97,10 @@ def test_refusals_name_the_argument():
         ConvTasNetStreamer(m, streams=0)
     with pytest.raises(SehipError, match="chunk_frames=-1"):
         ConvTasNetStreamer(m, chunk_frames=-1)
+    with pytest.raises(SehipError, match="streams=True"):
+        ConvTasNetStreamer(m, streams=True)
+    with pytest.raises(SehipError, match="chunk_frames=True"):
+        ConvTasNetStreamer(m, chunk_frames=True)
     with pytest.raises(SehipError, match="model must be"):
         ConvTasNetStreamer(torch.nn.Linear(2, 2))
     dev = torch.device("cuda", 0)

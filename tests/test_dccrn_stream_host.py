@@ -162,7 +162,11 @@ def test_refusals_name_the_reason():
         DCCRNStreamer(m, streams=2.0)
     with pytest.raises(SehipError, match="chunk_frames=-1"):
         DCCRNStreamer(m, chunk_frames=-1)
-    dev = torch.device("cuda", 0)
+    with pytest.raises(SehipError, match="streams=True"):
+        DCCRNStreamer(m, streams=True)
+    with pytest.raises(SehipError, match="chunk_frames=True"):
+        DCCRNStreamer(m, chunk_frames=True)
+    dev =torch.device("cuda", 0)
     with pytest.raises(SehipError, match=r"x must have shape .*\[2, 1, 300\], got \[2, 300\]"):
         check_feed_input(torch.zeros(2, 300), 2, 300, dev)
     with pytest.raises(SehipError, match="dtype torch.float32, got torch.float64"):

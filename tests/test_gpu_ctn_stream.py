@@ -12,45 +12,14 @@ import pytest
 import torch
 
 import ctn_variants_ref as V
+from stream_util import Guarded, cs, lib_call, same_bits
 from util import load_golden, rel_err
 
 pytestmark = pytest.mark.gpu
 
 ULP_TOL = 2.0 ** -8 * 1.02
-PAD = 64                       # canary elements on either side of a guarded buffer
 FIX = V.FIXTURE_KW
 H_HOP = FIX["L"] // 2
-
-
-def lib_call(name, *a):
-    from sehip._lib import call
-    call(name, *a)
-
-
-def cs():
-    return torch.cuda.current_stream().cuda_stream
-
-
-class Guarded:
-    """a tensor between two canary bands inside one allocation"""
-
-    def __init__(self, t):
-        t = t.contiguous()
-        self.canary = {torch.float32: 1234.5, torch.bfloat16: -77.0, torch.int32: 0x5a5a5a5}[t.dtype]
-        self.full = torch.full((t.numel() + 2 * PAD,), self.canary, dtype=t.dtype, device="cuda")
-        self.t = self.full[PAD:PAD + t.numel()].view(t.shape)
-        self.t.copy_(t)
-
-    def intact(self):
-        return bool((self.full[:PAD] == self.canary).all()) and bool((self.full[-PAD:] == self.canary).all())
-
-
-def bits(t):
-    return t.contiguous().view(torch.int16) if t.dtype == torch.bfloat16 else t.contiguous().view(torch.int32)
-
-
-def same_bits(a, b):
-    return torch.equal(bits(a), bits(b))
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -310,13 +279,42 @@ def test_feed_refusals_and_state_bytes_on_device():
     assert st.pos.tolist() == [-1, -1]
 
 
+def private_model(mask="relu"):
+    """a model with the fixture's parameters that a test may change or move (the shared one stays as it is)"""
+    from sehip.model import ConvTasNet
+    model = ConvTasNet(sources=["None", "None"], **FIX, causal=True, norm_type="cLN", mask_nonlinear=mask)
+    model.load_state_dict(fixture()["model"].state_dict())
+    return model.cuda()
+
+
+@pytest.mark.parametrize("mask", ["relu", "softmax"])
+def test_capture_in_mid_clip_and_launch_count(mask):
+    """A graphed streamer whose graph is dropped after three chunks (the model's flat storage is re-created, so _sync_model packs the
+    weights again and forgets the captured chain) captures again with streams in mid-clip: the eager pass before the capture must
+    leave pos, phase, carry, history and tail as they were, so every later chunk and the flush have the bits of an eager streamer fed
+    the same clip.  Both count the 4 R X + 5 launches of a chunk (+ 1 with the softmax mask)."""
+    from sehip.model import ConvTasNetStreamer
+    S, Kc, n = 2, 3, 3 * H_HOP
+    model = private_model(mask)
+    x = signals(S, 8 * Kc, seed=11)
+    eager, gr = ConvTasNetStreamer(model, S, Kc), ConvTasNetStreamer(model, S, Kc, graph=True)
+    assert eager.launches == gr.launches == 0
+    want, tail = stream_all(eager, x)
+    for j in range(8):
+        if j == 3:
+            first, epoch = gr._graph, model.storage_epoch
+            model.cuda()
+            assert first is not None and model.storage_epoch != epoch
+        assert same_bits(gr.feed(x[..., j * n:(j + 1) * n].contiguous()), want[..., j * n:(j + 1) * n]), j
+    assert gr._graph is not None and gr._graph is not first
+    assert same_bits(gr.flush(), tail) and float(tail.abs().max()) > 0
+    assert eager.launches == gr.launches == 4 * FIX["R"] * FIX["X"] + 5 + (mask == "softmax")
+
+
 def test_refresh_weights_follows_the_parameters():
     """the product weights are packed at construction and on refresh_weights(), not per chunk"""
-    from sehip.model import ConvTasNet, ConvTasNetStreamer
-    src = fixture()["model"]
-    model = ConvTasNet(sources=["None", "None"], **FIX, causal=True, norm_type="cLN")
-    model.load_state_dict(src.state_dict())
-    model = model.cuda()
+    from sehip.model import ConvTasNetStreamer
+    model = private_model()
     x = signals(1, 8, seed=8)
     st = ConvTasNetStreamer(model, 1, 8)
     y0 = st.feed(x).clone()

@@ -18,11 +18,11 @@ import torch
 import dccrn_stream_ref as SR
 import frontend_ref as FR
 from oracle import dccrn_oracle as O
+from stream_util import Guarded, cs, lib_call, same_bits
 from util import rel_err
 
 pytestmark = pytest.mark.gpu
 
-PAD = 64                       # canary elements on either side of a guarded buffer
 GEOMETRIES = [(400, 100), (320, 160), (512, 128)]
 LA = 6
 NO_END = 2 ** 31 - 1
@@ -33,41 +33,6 @@ FFT_OPS = 50
 #   correction sums over the frame (tree sums, depth 9 + 6, + 5 for combining them), window and scale (3), R + 1 additions of the
 #   overlap-add, the reciprocal window energy and its product (2)
 SYN_OPS = 16 + FFT_OPS + 20 + 3 + 6 + 2
-
-
-def lib_call(name, *a):
-    from sehip._lib import call
-    call(name, *a)
-
-
-def cs():
-    return torch.cuda.current_stream().cuda_stream
-
-
-class Guarded:
-    """a tensor between two canary bands inside one allocation"""
-
-    def __init__(self, t):
-        t = t.contiguous()
-        self.canary = {torch.float32: 1234.5, torch.bfloat16: -77.0, torch.int32: 0x5a5a5a5}[t.dtype]
-        self.full = torch.full((t.numel() + 2 * PAD,), self.canary, dtype=t.dtype, device="cuda")
-        self.t = self.full[PAD:PAD + t.numel()].view(t.shape)
-        self.t.copy_(t)
-
-    @property
-    def ptr(self):
-        return self.t.data_ptr()
-
-    def intact(self):
-        return bool((self.full[:PAD] == self.canary).all()) and bool((self.full[-PAD:] == self.canary).all())
-
-
-def bits(t):
-    return t.contiguous().view(torch.int16) if t.dtype == torch.bfloat16 else t.contiguous().view(torch.int32)
-
-
-def same_bits(a, b):
-    return torch.equal(bits(a), bits(b.to(a.device)))
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -397,6 +362,32 @@ def test_bit_stability():
     assert a.pos.tolist() == [12, 21, 12]
     a.reset(torch.tensor([True, True, True]))
     assert a.pos.tolist() == [0, 0, 0]
+
+
+def test_capture_in_mid_clip_and_launch_count():
+    """A graphed streamer whose graph is dropped after three chunks (the model's flat storage is re-created, so _sync_model derives the
+    weights again and forgets the captured chain) captures again with streams in mid-clip: the eager pass before the capture must leave
+    every state tensor as it was, so every later chunk and the flush have the bits of an eager streamer fed the same clip.  Launches
+    per chunk: 36 + 4 per LSTM layer, the values of the streamer before ChunkStreamer counted them."""
+    from sehip.model import DCCRN, DCCRNStreamer
+    kw, cfg, p, x, _, _, _ = case()
+    model, xc, n = build(kw, p), x.cuda(), 300
+    eager, gr = DCCRNStreamer(model, streams=2, chunk_frames=3), DCCRNStreamer(model, streams=2, chunk_frames=3, graph=True)
+    assert eager.launches == gr.launches == 0
+    want, tail = stream_all(eager, xc)
+    for j in range(HOPS // 3):
+        if j == 3:
+            first, epoch = gr._graph, model.storage_epoch
+            model.cuda()
+            assert first is not None and model.storage_epoch != epoch
+        assert same_bits(gr.feed(xc[..., j * n:(j + 1) * n].contiguous()), want[..., j * n:(j + 1) * n]), j
+    assert gr._graph is not None and gr._graph is not first
+    assert same_bits(gr.flush(), tail) and float(tail.abs().max()) > 0
+    assert eager.launches == gr.launches == 44
+    for layers, launches in ((1, 40), (3, 48)):
+        st = DCCRNStreamer(DCCRN(**dict(kw, rnn_layers=layers)).cuda().eval(), streams=2, chunk_frames=3)
+        st.feed(xc[..., :n].contiguous())
+        assert st.launches == launches, layers
 
 
 def test_no_interference_with_the_models_own_step():

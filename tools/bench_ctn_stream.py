@@ -5,23 +5,13 @@ forward over the same total signal beside it as the baseline.
 
     python tools/bench_ctn_stream.py --out profiles/ctn_stream.json
 
-The parent process opens no GPU: every (S, Kc) cell runs in a child of its own (`--cell S KC`) under a time limit, and the first cell
-that fails or runs out of time ends the run (nothing more is started on the device after it).  In a cell the calls are queued back
+Every (S, Kc) cell runs in a child process of its own under a time limit (tools/stream_bench.py).  In a cell the calls are queued back
 to back -- the same chunk fed `frames / Kc` times, which is one pass over a signal of `frames` hops per stream -- and timed with a host
 clock between two device synchronisations, after a warm-up pass of the same length; `repeats` passes each, the median reported.
 """
-import argparse
 import json
-import os
-import statistics
-import subprocess
-import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "speech-enhancement-pytorch_amd")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+from stream_bench import main, timed
 
 STREAMS, CHUNKS = (1, 8, 64), (1, 8, 32)
 
@@ -37,17 +27,6 @@ def cell(S, Kc, frames, repeats):
     x = (0.3 * torch.randn(S, 1, Kc * h, generator=g)).cuda()
     whole = (0.3 * torch.randn(S, 1, (frames + 1) * h, generator=g)).cuda()
 
-    def timed(run):
-        run()                                   # warm-up: the same pass
-        torch.cuda.synchronize()
-        ms = []
-        for _ in range(repeats):
-            t0 = time.perf_counter()
-            run()
-            torch.cuda.synchronize()
-            ms.append((time.perf_counter() - t0) * 1e3)
-        return statistics.median(ms)
-
     out = {"streams": S, "chunk_frames": Kc, "chunks_per_pass": n, "chunk_ms_of_audio_at_16k": Kc * h / 16.0}
     for tag, graph in (("eager", False), ("graph", True)):
         st = ConvTasNetStreamer(model, streams=S, chunk_frames=Kc, graph=graph)
@@ -56,10 +35,10 @@ def cell(S, Kc, frames, repeats):
             for _ in range(n):
                 st.feed(x)
 
-        out[tag + "_ms_per_chunk"] = round(timed(run) / n, 5)
+        out[tag + "_ms_per_chunk"] = round(timed(run, repeats) / n, 5)
         assert bool(torch.isfinite(st.flush()).all())
     with torch.no_grad():
-        off = timed(lambda: model(whole))
+        off = timed(lambda: model(whole), repeats)
     out["offline_forward_ms"] = round(off, 5)
     out["offline_ms_per_chunk_equivalent"] = round(off / n, 5)
     out["state_bytes"] = st.state_bytes
@@ -67,40 +46,9 @@ def cell(S, Kc, frames, repeats):
     print("CELL " + json.dumps(out))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--cell", nargs=2, type=int, default=None, metavar=("S", "KC"))
-    ap.add_argument("--frames", type=int, default=640, help="hops per stream in one timed pass (a multiple of every Kc)")
-    ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--limit", type=int, default=120, help="seconds a cell may take")
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
-    if args.cell:
-        cell(args.cell[0], args.cell[1], args.frames, args.repeats)
-        return
-    cells = []
-    for S in STREAMS:
-        for Kc in CHUNKS:
-            cmd = [sys.executable, os.path.abspath(__file__), "--cell", str(S), str(Kc), "--frames", str(args.frames), "--repeats", str(args.repeats)]
-            try:
-                r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.limit)
-            except subprocess.TimeoutExpired:
-                sys.exit(f"cell S={S} Kc={Kc} ran out of its {args.limit} s: stopping")
-            line = next((ln for ln in r.stdout.splitlines() if ln.startswith("CELL ")), None)
-            if r.returncode != 0 or line is None:
-                sys.exit(f"cell S={S} Kc={Kc} failed with status {r.returncode}: stopping\n{r.stderr[-2000:]}")
-            cells.append(json.loads(line[5:]))
-            print(line, flush=True)
-    doc = {"what": "ConvTasNetStreamer, C4 widths, causal cLN: ms per chunk (median of the passes; calls queued back to back), eager and "
-                   "graphed, and the offline forward over the same total signal",
-           "frames_per_pass": args.frames, "repeats": args.repeats, "cells": cells}
-    text = json.dumps(doc, indent=1)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
-    else:
-        print(text)
+DOC = {"what": "ConvTasNetStreamer, C4 widths, causal cLN: ms per chunk (median of the passes; calls queued back to back), eager and "
+               "graphed, and the offline forward over the same total signal"}
 
 
 if __name__ == "__main__":
-    main()
+    main(__file__, cell, STREAMS, CHUNKS, 640, DOC)
