@@ -918,6 +918,35 @@ int sehip_unet_bn_bwd_reduce(const void* dz, const void* code, const void* y, co
 int sehip_unet_bn_bwd_apply(const void* dz, const void* code, const void* y, const float* coef, const float* bcoef, int R, int T, int F, int C,
                             unsigned seed_lo, unsigned seed_hi, const void* ctr, int layer, unsigned thresh, float scale, void* dy, void* stream);
 
+/* ---- STOI / ESTOI validation metric (src/metric.py:126-144 calls pystoi's stoi(clean, estimate, sr, extended=False) per utterance;
+ *      Taal et al. 2011, Jensen & Taal 2016), csrc/stoi.hip.  `rows` pairs of a clean and an estimated row, fp32, 1 <= rows <= 32767.
+ *      The number K of frames a row keeps is data-dependent and stays on the device: every launch is sized by the upper bound F =
+ *      sehip_stoi_frames(len) and nothing is read back.  No atomics, fixed summation order, arguments validated before any HIP call.
+ *      out_len        : ceil(n p / q) samples at 10 kHz for n samples at sr (p / q = 10000 / sr reduced), -1 for n < 0, n > 2^30, sr <= 0
+ *      frames         : F = (len - 256) / 128 + 1 frames of 256 samples at hop 128, 0 for len < 256 or len > 2^30
+ *      segment_blocks : records per row of `partial` for sehip_stoi_segments
+ *      resample       : out [2 rows][out_len(n)] (clean rows, then estimate rows); out[m] = sum_i table[r][i] x[k - i] with k = (m q + L) / p,
+ *                       r = (m q + L) % p, zeros outside x; table [p][2 L / p + 1] = p w[r + i p] of the normalised Kaiser-windowed sinc w
+ *                       of 2 L + 1 taps (sehip/metric.py: stoi_resample_table).  Reduced ratio, p <= 128, q <= 1024, p != q
+ *      levels         : level [rows][F] = 20 log10(||win * frame|| + eps) of the clean rows [rows][len], win = hanning(258)[1:-1]
+ *      select         : kept[row] = K, src[row][j < K] = index of the j-th frame whose level is within 40 dB of the row's maximum
+ *      bands          : tob [2][rows][15][F - 1] (clean, then estimate): the one-third-octave band magnitudes of frame t < K - 1 of the
+ *                       row's compacted signal (kept windowed frames overlap-added at hop 128, windowed again, 512-point transform);
+ *                       entries t >= K - 1 are not written
+ *      segments       : d[row] = the 30-frame sliding correlation (extended 0: scaled, clipped at -15 dB SDR, per band; 1: normalised along
+ *                       time, then along the bands), 1e-5 for rows with fewer than 30 frames; out[0] = mean of d; partial
+ *                       [rows][segment_blocks(F, extended)] is scratch */
+long sehip_stoi_out_len(long n, int sr);
+int sehip_stoi_frames(long len);
+int sehip_stoi_segment_blocks(int F, int extended);
+int sehip_stoi_resample(const float* clean, const float* est, int rows, long n, const float* table, int p, int q, int L, float* out,
+                        void* stream);
+int sehip_stoi_levels(const float* clean, int rows, long len, float* level, void* stream);
+int sehip_stoi_select(const float* level, int rows, int F, int* kept, int* src, void* stream);
+int sehip_stoi_bands(const float* clean, const float* est, int rows, long len, const int* kept, const int* src, float* tob, void* stream);
+int sehip_stoi_segments(const float* tob, const int* kept, int rows, int F, int extended, float* partial, float* d, float* out,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,5 +8,6 @@ compute entry points raise SehipError.
 from ._lib import SehipError, lib, LIB_PATH  # noqa: F401
 from .ha import NALRTorch, CompressorTorch  # noqa: F401
 from .audio import amplify_torch, convert_audio_channels  # noqa: F401
+from .metric import SI_SDR, STOI  # noqa: F401
 
 __version__ = "0.1.0"

@@ -8,7 +8,9 @@ model_<epoch>_<metric>_<best>.pth, best_model.tar, state.json), resume / preload
 Changed by design: one process per GPU with an RCCL all-reduce of the flat gradient buffer instead of
 nn.DataParallel (src/solver.py:144-145); clip + optimizer are one fused launch; per-step `.item()` syncs happen
 every `config.solver.log_interval` steps (default 1 = the reference's cadence); no CUDA_LAUNCH_BLOCKING.
-Out of scope: inference / metrics / plots (src/solver.py:534-746).
+Validation can select checkpoints by `validation.metric: 'sisdr'` or `'stoi'` (sehip/metric.py, on the device) as well as by 'loss';
+compute_metric() is src/solver.py:704-721 on device tensors.
+Out of scope: inference / PESQ, HASPI, HASQI / plots (src/solver.py:534-746).
 """
 import datetime
 import json
@@ -270,7 +272,8 @@ class Solver(object):
                 break
             print(f"[{int(time.time() - start_time)} seconds] End this epoch.")
 
-    def _prepare_batch(self, mixture, sources):
+    def _prepare_batch(self, mixture, sources, wave=False):
+        """wave=True stops before the STFT of the STFT-domain models: the time-domain pair the validation metrics are taken on"""
         cfg = self.config
         mixture = mixture.to(self.device, non_blocking=True)
         sources = sources.to(self.device, non_blocking=True)
@@ -284,6 +287,8 @@ class Solver(object):
             sources = torch.squeeze(sources, dim=1)
             mixture = torch.reshape(mixture, shape=(batch * nchannel, 1, nsample))
             sources = torch.reshape(sources, shape=(batch * num_spk * nchannel, 1, nsample))
+        if wave:
+            return mixture, sources
         if cfg.model.name in STFT_MODELS:
             # src/solver.py:454-458: mixture and sources go to the STFT domain [B, C, F, T, 2] and the loss is taken there.
             # HIP kernels on the GPU; torch.stft only in the explicit CPU plumbing configuration (sehip/plumbing.py)
@@ -291,6 +296,40 @@ class Solver(object):
             mixture = stft(tensor=mixture, config=cfg.model)
             sources = stft(tensor=sources, config=cfg.model)
         return mixture, sources
+
+    # ---- validation metrics (src/solver.py:704-721, src/metric.py) ---------------------------------------
+    def _metric_functions(self):
+        from . import metric
+        return {"sisdr": metric.SI_SDR, "stoi": metric.STOI}
+
+    def _sample_rate(self):
+        return int(_cfg(getattr(self.config, "dset", None), "sample_rate", 16000))
+
+    def compute_metric(self, mixture, enhanced, clean):
+        """src/solver.py:704-721 on device waveforms [..., T]: -> (score, score_reference), dicts with the keys 'sisdr' and 'stoi', each a
+        one-element list holding a 0-dim device tensor (the enhanced signal's / the mixture's value against `clean`).  No 'pesq' key:
+        PESQ is out of scope.  The sample rate is config.dset.sample_rate (16000 when the configuration has none: the default the
+        reference's metrics are called with)."""
+        sr = self._sample_rate()
+        score, score_reference = {}, {}
+        with torch.no_grad():
+            for name, fn in self._metric_functions().items():
+                score_reference[name] = [fn(reference=clean, estimation=mixture, sr=sr)]
+                score[name] = [fn(reference=clean, estimation=enhanced, sr=sr)]
+        return score, score_reference
+
+    def _validation_metric(self, name, enhanced, wave_sources):
+        """The validation metric of one batch as a device scalar: enhanced is the model's output (a spectrum for the STFT-domain
+        models, taken back to the time domain here), wave_sources the time-domain sources of _prepare_batch(wave=True)."""
+        if self.config.model.name in STFT_MODELS:
+            from .evaluate import istft_custom
+            enhanced = istft_custom(enhanced.contiguous(), wave_sources.shape[-1], self.config.model)
+        if enhanced.shape != wave_sources.shape:
+            if enhanced.numel() != wave_sources.numel():
+                raise SehipError(f"validation metric '{name}': output {tuple(enhanced.shape)} and sources {tuple(wave_sources.shape)} "
+                                 "do not pair up")
+            enhanced = enhanced.reshape(wave_sources.shape)
+        return self._metric_functions()[name](reference=wave_sources, estimation=enhanced, sr=self._sample_rate())
 
     def train_step(self, mixture, sources):
         """One optimisation step on device tensors; returns (loss, grad_metric[2]) as DEVICE tensors (no sync)."""
@@ -460,12 +499,19 @@ class Solver(object):
             elif not train and total_step > cfg.solver.validation.total_steps:
                 total_step = cfg.solver.validation.total_steps
         pending = []  # device scalars waiting for the next logging point
+        # validation.metric 'stoi' / 'sisdr': taken per batch on waveforms, queued with the losses ('loss': nothing is added to the loop)
+        valid_metric = cfg.solver.validation.metric if not train and cfg.solver.validation.metric in ("stoi", "sisdr") else None
+        score_total, score_steps = 0.0, 0
 
         def flush():
-            nonlocal loss_total, grad_norm_total
+            nonlocal loss_total, grad_norm_total, score_total, score_steps
             for step_, loss_t, metric_t in pending:
                 loss = float(loss_t)
                 loss_total += loss
+                if valid_metric is not None:
+                    score_total += float(metric_t)
+                    score_steps += 1
+                    self.score[valid_metric] = score_total / score_steps
                 if train:
                     grad_norm = float(metric_t[0]) if metric_t is not None else 0.0
                     grad_norm_total += grad_norm
@@ -483,6 +529,8 @@ class Solver(object):
             if step >= total_step:
                 break
             mixture, sources = batch[0], batch[1]
+            if valid_metric is not None and cfg.model.name in STFT_MODELS:
+                wave_sources = self._prepare_batch(mixture, sources, wave=True)[1]
             mixture, sources = self._prepare_batch(mixture, sources)
             if train:
                 step_fn = self.train_step_graphed if _cfg(cfg.solver, "use_graph", False) else self.train_step
@@ -495,7 +543,11 @@ class Solver(object):
                 with torch.no_grad():
                     enhanced = self.model(mixture)
                     loss_t = self._loss(enhanced, sources, mixture)
-                pending.append((step, loss_t.detach().clone(), None))
+                    score_t = None
+                    if valid_metric is not None:
+                        score_t = self._validation_metric(valid_metric, enhanced,
+                                                          wave_sources if cfg.model.name in STFT_MODELS else sources)
+                pending.append((step, loss_t.detach().clone(), score_t))
             if (step + 1) % self.log_interval == 0:
                 flush()
         flush()
