@@ -883,6 +883,39 @@ int sehip_ha_compressor_fwd(const float* z, long rows, long n, int W, double thr
                             double attenuation, int soft_clip, double* ws, float* gain, float* out, void* stream);
 int sehip_ha_compressor_bwd(const float* dout, const float* out, const float* gain, long count, int soft_clip, float* dz, void* stream);
 
+/* ---- hearing-aid back end, chunk by chunk (csrc/ha_stream.hip; sehip.ha.AmplifyStreamer).  The stage above for rows that resume from
+ *      state carried on the device.  C = chunk_samples in [1, 65536] is the largest chunk, a call takes 1 <= n <= C samples per row;
+ *      1 <= rows <= 65535, K in [1, 1025], W in [1, 2^20].  State of row r (a fresh row: pos = 0, c = 1; the rings need no clearing,
+ *      a sample index below 0 reads as zero):
+ *        pos   [rows] int64            samples fed so far
+ *        xring [rows][K - 1 + C] fp32  input sample a at slot a mod (K - 1 + C)
+ *        zring [rows][W - 1 + C] fp32  filtered sample a at slot a mod (W - 1 + C)
+ *        c     [rows] float64          the compressor's c after sample pos - 1
+ *      The rings are one chunk longer than their history, so the slots a call writes are never the slots it reads.  Work buffers
+ *      xin, filt, gain, out are [rows][C] fp32 (row stride C, the first n columns used); c_next [rows] float64.  One chunk is the three
+ *      calls below in this order with the same arguments (the position is read on the device): capturable into a hipGraph.  Arguments
+ *      are validated before any HIP call; no atomics, nothing synchronises or reads back; the same bits from run to run.
+ *        sehip_has_state_bytes: bytes of pos, xring, zring and c (host-only; 0 for sizes outside the ranges above)
+ *        sehip_has_fir:      with x(a) = xin[r][a - pos] for a >= pos, xring's sample a for pos - K < a < pos, 0 for a < 0:
+ *                              filt[r][m] = sum_{k < K} h[f_r][k] * x(pos + m - k),  m in [0, n)
+ *                            one fmaf chain over k = 0 .. K - 1 from 0, as sehip_ha_fir_fwd: the bits of that entry on the whole
+ *                            input.  Also stores xin into xring and filt into zring at samples pos .. pos + n - 1.  taps, F, row_set
+ *                            as sehip_ha_fir_fwd.
+ *        sehip_has_compress: z(a) = zring's sample a (0 for a < 0); for i = pos + j, j in [0, n):
+ *                              lv_i = sqrt((sum of z(a)^2, a in (i - W, i]) / W + 1e-8)
+ *                              (a, b)_i as sehip_ha_compressor_fwd;  c_i = a_i * c_{i-1} + b_i,  c_{pos-1} = c[r]
+ *                              gain[r][j] = fp32(c_i);  out[r][j] = z(i) * gain[r][j], tanh of it if soft_clip;  c_next[r] = c_{pos+n-1}
+ *                            The window sums are float64 sums of non-negative terms over the stored samples, formed afresh in every
+ *                            call (a suffix of the outgoing samples + the untouched middle + a prefix of the incoming ones): nothing
+ *                            but c is carried from call to call, no difference of sums is taken.
+ *        sehip_has_advance:  pos[r] += n, c[r] = c_next[r] */
+long sehip_has_state_bytes(long rows, int K, int W, int C);
+int sehip_has_fir(const float* xin, long rows, int n, int C, const float* taps, int F, int K, int W, const int* row_set /*or NULL*/,
+                  const long* pos, float* xring, float* zring, float* filt, void* stream);
+int sehip_has_compress(const float* zring, long rows, int n, int C, int W, const long* pos, const double* c, double threshold, double attack,
+                       double release, double attenuation, int soft_clip, double* c_next, float* gain, float* out, void* stream);
+int sehip_has_advance(long* pos, double* c, const double* c_next, long rows, int n, void* stream);
+
 /* ---- U-Net on the power spectrogram (src/model/unet.py:9-146, `unet`; csrc/unet.hip).  Activations are channels-last bf16
  *      [R][T_l][F_l][C] (T frames, F rows per frame, both halved by floor per level), C a power of two >= 8, at most 2^32 elements per
  *      tensor (the dropout index is 32 bits wide); spec / out / dout are fp32 [R][uc][F][T][2].  Cp = uc rounded up to a multiple of 8:

@@ -6,7 +6,7 @@ There is no CPU or stock-PyTorch fallback: on a machine without the library or w
 compute entry points raise SehipError.
 """
 from ._lib import SehipError, lib, LIB_PATH  # noqa: F401
-from .ha import NALRTorch, CompressorTorch  # noqa: F401
+from .ha import NALRTorch, CompressorTorch, AmplifyStreamer  # noqa: F401
 from .audio import amplify_torch, convert_audio_channels  # noqa: F401
 from .metric import SI_SDR, STOI  # noqa: F401
 
