@@ -916,6 +916,40 @@ int sehip_has_compress(const float* zring, long rows, int n, int C, int W, const
                        double release, double attenuation, int soft_clip, double* c_next, float* gain, float* out, void* stream);
 int sehip_has_advance(long* pos, double* c, const double* c_next, long rows, int n, void* stream);
 
+/* ---- julius.resample_frac, chunk by chunk (csrc/resample_stream.hip; sehip.ResampleStreamer).  sehip_resample_frac above for rows that
+ *      resume from state carried on the device.  old_sr / new_sr, width as there (the REDUCED ratio, terms in [1, 1024], width in
+ *      [1, 65536]); K = 2 * width + old_sr.  The new_sr outputs y[q * new_sr + p], p < new_sr, are frame q; a frame consumes old_sr input
+ *      samples and reads input up to sample q * old_sr + width + old_sr - 1.  With
+ *          Dq = ceil(width / old_sr)   (sehip_rss_delay_frames)        H = Dq * old_sr + width   (the history a call needs)
+ *      a call that takes the input frames F .. F + f - 1 returns the output frames F - Dq .. F + f - 1 - Dq: the offline output delayed
+ *      by Dq * new_sr samples; a frame q < 0 is exact zeros.  C = chunk_frames in [1, 4096] is the largest chunk, 1 <= f <= C;
+ *      1 <= rows <= 65535.  State of row r (a fresh row: pos = 0; the ring needs no clearing, a sample index below 0 reads sample 0):
+ *        pos   [rows] int64                       input frames fed so far
+ *        ring  [rows][H + C * old_sr] fp32        input sample a at slot a mod (H + C * old_sr)
+ *      The ring is one chunk longer than the history, so the slots a call writes are never the slots it reads.  Work buffers: xin
+ *      [rows][C * old_sr], out [rows][C * new_sr] fp32 (row strides of a whole chunk, the first f frames used).  One chunk is the two
+ *      calls below in this order with the same arguments (the position is read on the device): capturable into a hipGraph.  Arguments
+ *      are validated before any HIP call; no atomics, nothing synchronises or reads back; the same bits from run to run.
+ *        sehip_rss_delay_frames: Dq (host-only; -1 for a ratio or width outside the ranges above)
+ *        sehip_rss_state_bytes:  rows * (8 + 4 * (H + C * old_sr)): pos and ring (host-only; 0 for sizes outside the ranges above)
+ *        sehip_rss_feed:     table_t [K][new_sr] fp32 is the TRANSPOSE of sehip_resample_frac's kernels.  With x(i) the row's sample
+ *                            at chunk index i (i >= 0: xin[r][i]; i < 0: the ring's sample pos * old_sr + i), an index with
+ *                            pos * old_sr + i < 0 reading stream sample 0 and, if end_len >= 0, an index i >= end_len reading
+ *                            x(end_len - 1):
+ *                              out[r][g * new_sr + p] = sum_{k < K} table_t[k][p] * x((g - Dq) * old_sr + k - width),  g in [0, f),
+ *                            and zero where pos + g - Dq < 0.  Each sum is formed by one thread with fused multiply-adds in the order
+ *                            of the kernel that sehip_resample_frac runs for the ratio (csrc/resample_plan.h): the bits of that entry
+ *                            on the whole input.  Also stores x(0 .. f * old_sr - 1) into the ring at frames pos .. pos + f - 1.
+ *                            end_len < 0: the stream goes on.  end_len in [0, f * old_sr]: the row's last sample is chunk sample
+ *                            end_len - 1 (0: the sample before the chunk) -- offline's right-hand clamp; the ring then holds the
+ *                            replicate-padded stream, so further calls with end_len = 0 continue the tail.
+ *        sehip_rss_advance:  pos[r] += f */
+long sehip_rss_delay_frames(int old_sr, int new_sr, int width);
+long sehip_rss_state_bytes(long rows, int old_sr, int new_sr, int width, int chunk_frames);
+int sehip_rss_feed(const float* xin, long rows, int frames, int chunk_frames, const float* table_t, int old_sr, int new_sr, int width,
+                   const long* pos, float* ring, long end_len, float* out, void* stream);
+int sehip_rss_advance(long* pos, long rows, int frames, void* stream);
+
 /* ---- U-Net on the power spectrogram (src/model/unet.py:9-146, `unet`; csrc/unet.hip).  Activations are channels-last bf16
  *      [R][T_l][F_l][C] (T frames, F rows per frame, both halved by floor per level), C a power of two >= 8, at most 2^32 elements per
  *      tensor (the dropout index is 32 bits wide); spec / out / dout are fp32 [R][uc][F][T][2].  Cp = uc rounded up to a multiple of 8:

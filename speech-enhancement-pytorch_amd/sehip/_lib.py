@@ -236,6 +236,10 @@ _PROTOS = {
     "sehip_has_fir": [P, L, I, I, P, I, I, I, P, P, P, P, P, P],
     "sehip_has_compress": [P, L, I, I, I, P, P, D, D, D, D, I, P, P, P, P],
     "sehip_has_advance": [P, P, P, L, I, P],
+    "sehip_rss_delay_frames": [I, I, I],
+    "sehip_rss_state_bytes": [L, I, I, I, I],
+    "sehip_rss_feed": [P, L, I, I, P, I, I, I, P, P, L, P, P],
+    "sehip_rss_advance": [P, L, I, P],
     "sehip_unet_features": [P, I, I, I, I, I, P, P],
     "sehip_unet_mask_fwd": [P, P, P, I, I, I, I, I, P, P],
     "sehip_unet_mask_bwd": [P, P, I, I, I, I, I, P, P],
@@ -245,7 +249,7 @@ _PROTOS = {
     "sehip_unet_bn_bwd_reduce": [P, P, P, P, I, I, I, I, U, U, P, I, U, F, P, P],
     "sehip_unet_bn_bwd_apply": [P, P, P, P, P, I, I, I, I, U, U, P, I, U, F, P, P],
 }
-_RESTYPE = {"sehip_resample_out_len": C.c_long, "sehip_stoi_out_len": C.c_long,"sehip_ha_compressor_ws_doubles": C.c_long, "sehip_has_state_bytes": C.c_long,"sehip_rsm_sum_scratch_floats": C.c_long, "sehip_wun_bn_scratch_floats": C.c_long, "sehip_wun_enc0_wgrad_scratch_floats": C.c_long, "sehip_wun_out_bwd_scratch_floats": C.c_long,
+_RESTYPE = {"sehip_resample_out_len": C.c_long, "sehip_stoi_out_len": C.c_long,"sehip_ha_compressor_ws_doubles": C.c_long, "sehip_has_state_bytes": C.c_long, "sehip_rss_delay_frames": C.c_long, "sehip_rss_state_bytes": C.c_long, "sehip_rsm_sum_scratch_floats": C.c_long, "sehip_wun_bn_scratch_floats": C.c_long, "sehip_wun_enc0_wgrad_scratch_floats": C.c_long, "sehip_wun_out_bwd_scratch_floats": C.c_long,
             "sehip_lstm2_gran_bytes": C.c_long, "sehip_dmx_attn_bwd_scratch_floats": C.c_long, "sehip_ctn_codec_bwd_scratch_floats": C.c_long, "sehip_ctn_gln_bwd_scratch_floats": C.c_long, "sehip_ctn_cln_bwd_scratch_floats": C.c_long, "sehip_wgrad_group_bytes": C.c_long, "sehip_wgrad_dense_group_bytes": C.c_long, "sehip_cbn_scratch_floats": C.c_long, "sehip_rbn_scratch_floats": C.c_long, "sehip_dcunet_tail_scratch_floats": C.c_long, "sehip_event_create": C.c_void_p, "sehip_stream_create": C.c_void_p}
 
 

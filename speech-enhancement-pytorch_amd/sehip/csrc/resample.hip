@@ -21,16 +21,13 @@
 //                              output sample straight from global memory.  Correct for every accepted argument, not tuned.
 #include <mutex>
 #include "common.h"
+#include "resample_plan.h"
 
 namespace {
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 constexpr int RS_MAX_TERM = 1024;
 constexpr int RS_MAX_WIDTH = 1 << 16;
 constexpr int RS_MAX_DEVICES = 64;
-constexpr size_t RS_LDS_MAX = 160 * 1024;
-constexpr int RS_WAVES = 16;         // phase kernel: 1024 threads, 4 waves per SIMD behind the scalar loads' latency
-constexpr int RS_DT = 8;             // decim kernel: consecutive outputs per thread
-constexpr int RS_DF = 256 * RS_DT;   //               outputs per tile
 
 __device__ __forceinline__ long rs_clamp(long i, long n) { return i < 0 ? 0 : (i > n - 1 ? n - 1 : i); }
 
@@ -229,45 +226,27 @@ extern "C" int sehip_resample_frac(const float* raw, const long* row_off, int ro
     hipStream_t st = (hipStream_t)stream;
     const hipError_t prep = rs_prepare_device();
     if (prep != hipSuccess) return sehip_set_error(-2, "resample_frac: cannot raise the kernels' LDS limit: %s", hipGetErrorString(prep));
-    const long K = 2L * width + old_sr, J = (K + old_sr - 1) / old_sr;
+    const rs_plan pl = rs_make_plan(old_sr, new_sr, width);         // (resample_plan.h: the streamer follows the same decision)
+    const long K = pl.K;
     int gx = 2048 / rows;                                         // blocks per row; a block strides over its row's tiles
     gx = gx < 1 ? 1 : (gx > 1024 ? 1024 : gx);
-    if (new_sr == 1) {
-        const long W = (long)(RS_DF - 1) * old_sr + K;
-        const size_t lds = (size_t)(W + ((W / old_sr) >> 3) + 8) * sizeof(float);
-        if (lds <= RS_LDS_MAX) {
-            resample_decim_kernel<<<dim3(gx, rows), 256, lds, st>>>(raw, row_off, kernels, old_sr, width, out, out_off);
-            SEHIP_CHECK_LAUNCH("resample_frac (decim)");
-            sehip_note_kernel("resample_decim old=%d K=%ld lds=%zu", old_sr, K, lds);
-            return 0;
-        }
+    if (pl.kind == RS_DECIM) {
+        resample_decim_kernel<<<dim3(gx, rows), 256, pl.lds, st>>>(raw, row_off, kernels, old_sr, width, out, out_off);
+        SEHIP_CHECK_LAUNCH("resample_frac (decim)");
+        sehip_note_kernel("resample_decim old=%d K=%ld lds=%zu", old_sr, K, pl.lds);
+        return 0;
     }
-    int os = (old_sr + 3) & ~3;                                   // LDS row stride: a multiple of 4 words that is 4 (mod 8)
-    if ((os & 7) == 0) os += 4;
-    // P phases per lane and wf of the 16 waves along frames (the rest along phase groups): the pair with the least estimated
-    // wave-time per frame, rounds * (P + 2) / wf -- P pairs of FMAs per tap quad plus ~2 for the LDS read, the scalar loads' issue
-    // and the loop; a tie goes to the larger P.  (An estimate: measured at 441 -> 160 only)
-    int P = 0, wf = 0;
-    long best = 0;
-    for (int p = 8; p >= 1; p >>= 1) {
-        if (p > 1 && p / 2 >= new_sr) continue;                   // more than half of the phases would be padding
-        const int groups = (new_sr + p - 1) / p;
-        int w = RS_WAVES;
-        while (w > 1 && (RS_WAVES / w < groups || (size_t)(64 * w + J) * os * sizeof(float) > RS_LDS_MAX)) w >>= 1;
-        const long rounds = (groups + RS_WAVES / w - 1) / (RS_WAVES / w), cost = rounds * (p + 2) * RS_WAVES / w;
-        if (!P || cost < best) { P = p; wf = w; best = cost; }
-    }
-    const size_t lds = (size_t)(64 * wf + J) * os * sizeof(float);
-    if (lds <= RS_LDS_MAX) {
+    if (pl.kind == RS_PHASE) {
         const dim3 grid(gx, rows);
-#define RS_LAUNCH(PP) resample_phase_kernel<PP><<<grid, 64 * RS_WAVES, lds, st>>>(raw, row_off, kernels, old_sr, new_sr, width, os, wf, out, out_off)
-        if (P == 8) RS_LAUNCH(8);
-        else if (P == 4) RS_LAUNCH(4);
-        else if (P == 2) RS_LAUNCH(2);
+        const int os = pl.os, wf = pl.wf;
+#define RS_LAUNCH(PP) resample_phase_kernel<PP><<<grid, 64 * RS_WAVES, pl.lds, st>>>(raw, row_off, kernels, old_sr, new_sr, width, os, wf, out, out_off)
+        if (pl.P == 8) RS_LAUNCH(8);
+        else if (pl.P == 4) RS_LAUNCH(4);
+        else if (pl.P == 2) RS_LAUNCH(2);
         else RS_LAUNCH(1);
 #undef RS_LAUNCH
         SEHIP_CHECK_LAUNCH("resample_frac (phase)");
-        sehip_note_kernel("resample_phase P=%d wf=%d old=%d new=%d K=%ld lds=%zu", P, wf, old_sr, new_sr, K, lds);
+        sehip_note_kernel("resample_phase P=%d wf=%d old=%d new=%d K=%ld lds=%zu", pl.P, wf, old_sr, new_sr, K, pl.lds);
         return 0;
     }
     resample_direct_kernel<<<dim3(gx, rows), 256, 0, st>>>(raw, row_off, kernels, old_sr, new_sr, width, out, out_off);
