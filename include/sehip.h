@@ -1014,6 +1014,28 @@ int sehip_stoi_bands(const float* clean, const float* est, int rows, long len, c
 int sehip_stoi_segments(const float* tob, const int* kept, int rows, int F, int extended, float* partial, float* d, float* out,
                         void* stream);
 
+/* ---- STOI / ESTOI as a training loss: the backward pass of the launches above with respect to the ESTIMATE (sehip.loss.stoi_loss),
+ *      csrc/stoi_loss.hip.  kept / src / tob are what the forward launches left; the kept-frame set is a constant, sqrt at exactly 0 has
+ *      derivative 0, the clip passes the gradient to the branch the forward took (c y on a tie), a row with fewer than 30 spectra gets
+ *      exact zeros.  Gather form: every output element stored once, fixed summation order, no atomics, nothing read back.
+ *      segment_floats : floats of the scratch `seg` of sehip_stoil_segments, -1 for rows <= 0 or F <= 0
+ *      segments       : seg [rows][max(F - 30, 1)][15][30] = d(segment m's correlation term) / d(its 30 estimate cells of band b); then
+ *                       dtob [rows][15][F - 1] = -gout[row gstride] scale / (div M) times the sum over the segments that contain frame t,
+ *                       ascending (div = 15, extended 30; M = kept - 30), zero past a row's T and for a row without a segment.  gstride 0:
+ *                       one gradient for all rows (scale = 1 / rows for the mean), 1: one per row
+ *      bands          : fgrad [rows][F - 1][256], written for t < kept - 1 of the rows with a segment: the gradient of the estimate's frame
+ *                       t of the compacted signal (window applied); est [rows][len] is the estimate at 10 kHz
+ *      compact        : inv [rows][F] = compacted index of original frame f or -1; out [rows][len] = the gradient of the estimate at
+ *                       10 kHz, exact zeros for samples that lie only in dropped frames or past the last frame
+ *      resample_adj   : out [rows][n] = the adjoint of sehip_stoi_resample applied to g [rows][ceil(n p / q)] (same table and limits) */
+long sehip_stoil_segment_floats(int rows, int F);
+int sehip_stoil_segments(const float* tob, const int* kept, int rows, int F, int extended, const float* gout, int gstride, float scale,
+                         float* seg, float* dtob, void* stream);
+int sehip_stoil_bands(const float* est, int rows, long len, const int* kept, const int* src, const float* tob, const float* dtob,
+                      float* fgrad, void* stream);
+int sehip_stoil_compact(const float* fgrad, const int* kept, const int* src, int rows, long len, int* inv, float* out, void* stream);
+int sehip_stoil_resample_adj(const float* g, int rows, long n, const float* table, int p, int q, int L, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,7 @@ import torch
 import torch.distributed as dist
 
 from ._lib import SehipError
-from .loss import loss_sisdr, l1_loss, mse_loss, loss_phase_sensitive_spectral_approximation
+from .loss import loss_sisdr, l1_loss, mse_loss, loss_phase_sensitive_spectral_approximation, StoiLoss
 from .model.dccrn import DCCRN
 from .model.conv_tasnet import ConvTasNet
 from .model.dcunet import DCUnet
@@ -64,6 +64,8 @@ def get_loss_function(config, device="gpu"):
         return loss_sisdr
     if config.loss == "psa":      # src/distrib.py:270-271; the Solver passes the mixture as the third argument (Solver._loss)
         return loss_phase_sensitive_spectral_approximation
+    if config.loss in ("stoi", "estoi"):      # negated STOI / ESTOI of the waveforms; the Solver sets the sample rate (Solver._sample_rate)
+        return StoiLoss(extended=config.loss == "estoi")
     raise ValueError(f"Loss function {config.loss} cannot use...")
 
 

@@ -245,3 +245,164 @@ def loss_phase_sensitive_spectral_approximation(enhance, target, mixture):
         raise SehipError(f"psa loss: three [..., 2] tensors of one shape expected, got {tuple(enhance.shape)}, {tuple(target.shape)}, "
                          f"{tuple(mixture.shape)}")
     return _PsaLoss.apply(enhance, target, mixture)
+
+
+# ---- STOI / ESTOI as a loss (csrc/stoi_loss.hip behind the forward launches of csrc/stoi.hip) ------------------------------------------
+_stoi_loss_workspaces = {}    # (rows, n, sr, extended, device) -> StoiLossWorkspace of the functional form; a StoiLoss module owns its own
+
+
+class StoiLossWorkspace:
+    """Every buffer of one stoi_loss call on `rows` pairs of n samples at sr, forward and backward: the forward's (as
+    sehip.metric.stoi_workspace, but never shared with the metric, so a STOI() call between a forward and its backward changes nothing)
+    plus the value pair and the backward's scratch.  `generation` counts the forward passes: a backward pass whose forward is no longer
+    the latest one on these buffers is refused instead of differentiating the wrong call."""
+
+    def __init__(self, rows, n, sr, device):
+        from . import metric
+        from ._lib import lib
+        self.fwd = metric.stoi_buffers(rows, n, sr, device, "stoi_loss")     # the forward's own: p, q, n10, frames, table, sig, kept, src, tob
+        for k, v in self.fwd.items():
+            setattr(self, k, v)
+        f32 = dict(device=self.kept.device, dtype=torch.float32)
+        spectra = max(self.frames - 1, 1)
+        self.rows, self.n, self.sr = rows, n, int(sr)
+        self.d = torch.empty(rows, **f32)
+        self.mean = torch.empty((), **f32)
+        self.seg = torch.empty(lib().sehip_stoil_segment_floats(rows, self.frames), **f32)
+        self.dtob = torch.empty(rows, metric.STOI_BANDS, spectra, **f32)
+        self.fgrad = torch.empty(rows, spectra, metric.STOI_FRAME, **f32)
+        self.inv = torch.empty(rows, self.frames, device=self.kept.device, dtype=torch.int32)
+        self.g10 = None if self.sig is None else torch.empty(rows, self.n10, **f32)
+        self.generation = 0
+
+
+def _stoi_loss_check(enhanced, sources, what="stoi_loss"):
+    """the metric's refusals, before anything is allocated or launched"""
+    from ._lib import require_gpu
+    if not torch.is_tensor(enhanced) or not torch.is_tensor(sources):
+        raise SehipError(f"{what}: needs device tensors")
+    require_gpu(enhanced, what)
+    require_gpu(sources, what)
+    if enhanced.shape != sources.shape:
+        raise ValueError(f"{what}: shapes differ: {tuple(enhanced.shape)} vs {tuple(sources.shape)}")
+    if enhanced.dim() < 1 or enhanced.numel() == 0:
+        raise SehipError(f"{what}: empty input of shape {tuple(enhanced.shape)}")
+
+
+def stoi_loss_workspace(shape, sr=16000, extended=False, device="cuda"):
+    """The cached workspace of the functional stoi_loss / stoi_loss_rows for inputs of `shape` [..., T].  The loss fetches it itself; a
+    caller that records the loss into a hipGraph calls this BEFORE the capture begins, so that the recording allocates nothing but
+    the call's results."""
+    from . import metric
+    n = int(shape[-1])
+    rows = 1
+    for s in shape[:-1]:
+        rows *= int(s)
+    key = (rows, n, int(sr), bool(extended), str(metric._device(device)))
+    ws = _stoi_loss_workspaces.get(key)
+    if ws is None:
+        ws = StoiLossWorkspace(rows, n, sr, device)
+        if not torch.cuda.is_current_stream_capturing():
+            _stoi_loss_workspaces[key] = ws    # (a buffer born inside a capture lives in that graph's pool: it serves that recording only)
+    return ws
+
+
+class _StoiLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, est, ref, ws, extended, per_row):
+        from . import metric
+        rows, n = ws.rows, ws.n
+        e = est.detach().reshape(rows, n).contiguous().float()
+        r = ref.detach().reshape(rows, n).contiguous().float()
+        ext = int(bool(extended))
+        metric.stoi_forward(r, e, ws.fwd, ext, ws.d, ws.mean)
+        ws.generation += 1
+        ctx.ws, ctx.ext, ctx.per_row, ctx.generation, ctx.shape = ws, ext, per_row, ws.generation, est.shape
+        ctx.save_for_backward(*([e] if ws.sig is None else []))   # off 10 kHz the backward pass reads the resampled estimate the forward left
+        return torch.neg(ws.d if per_row else ws.mean)
+
+    @staticmethod
+    def backward(ctx, g):
+        from ._lib import call, ptr, stream
+        ws = ctx.ws
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        if ws.generation != ctx.generation:
+            raise SehipError("stoi_loss: another forward pass ran on this workspace before this one's backward pass; give each loss that "
+                             "is live at the same time a StoiLoss module of its own")
+        rows, n, n10, frames = ws.rows, ws.n, ws.n10, ws.frames
+        g = g.reshape(rows if ctx.per_row else 1).contiguous().float()
+        st = stream()
+        est10 = ptr(ctx.saved_tensors[0]) if ws.sig is None else ptr(ws.sig[rows:])
+        grad = torch.empty(rows, n, device=g.device, dtype=torch.float32)
+        g10 = grad if ws.sig is None else ws.g10
+        call("sehip_stoil_segments", ptr(ws.tob), ptr(ws.kept), rows, frames, ctx.ext, ptr(g), int(ctx.per_row),
+             1.0 if ctx.per_row else 1.0 / rows, ptr(ws.seg), ptr(ws.dtob), st)
+        call("sehip_stoil_bands", est10, rows, n10, ptr(ws.kept), ptr(ws.src), ptr(ws.tob), ptr(ws.dtob), ptr(ws.fgrad), st)
+        call("sehip_stoil_compact", ptr(ws.fgrad), ptr(ws.kept), ptr(ws.src), rows, n10, ptr(ws.inv), ptr(g10), st)
+        if ws.sig is not None:
+            table, p, q, L = ws.table
+            call("sehip_stoil_resample_adj", ptr(g10), rows, n, ptr(table), p, q, L, ptr(grad), st)
+        return grad.view(ctx.shape), None, None, None, None
+
+
+def _stoi_loss(enhanced, sources, sr, extended, per_row, ws=None):
+    _stoi_loss_check(enhanced, sources)
+    if ws is None:
+        ws = stoi_loss_workspace(enhanced.shape, sr, extended, enhanced.device)
+    return _StoiLoss.apply(enhanced, sources, ws, bool(extended), per_row)
+
+
+def stoi_loss(enhanced, sources, sr=16000, extended=False):
+    """-mean over all rows of stoi(sources, enhanced, sr, extended) for device tensors [..., T] of equal shape (rows = every axis but the
+    last) -> 0-dim float32 device tensor: bit for bit the negation of sehip.metric.STOI(sources, enhanced, sr, extended), computed with
+    the same forward launches, and differentiable with respect to `enhanced` (csrc/stoi_loss.hip).  `sources` is the clean signal:
+    the frame selection follows it and it receives no gradient.
+
+    The gradient's conventions: the kept-frame set is a constant; sqrt at exactly 0 has derivative 0; the clip min(c y, 6.62 x) passes the
+    gradient to the branch the forward took (c y on a tie); a row with fewer than 30 spectra (value 1e-5) has gradient exactly zero.
+    No readbacks and no atomics, every sum in a fixed order: two runs give the same bits, and forward + backward can be captured into
+    one graph (stoi_loss_workspace(...) before the capture).  After the first call at a shape nothing but the results is allocated.
+
+    Limit of this functional form: all calls at one (rows, T, sr, extended, device) share one workspace, so only the LATEST forward pass
+    at a shape can be differentiated; the backward pass of an earlier one (two estimates against one target, say) raises SehipError.
+    Give each loss that is live at the same time a StoiLoss module of its own.  Workspaces stay allocated (a captured graph refers to
+    their buffers): one per shape, each with the backward's scratch of 450 floats per segment and 256 per spectrum and row."""
+    return _stoi_loss(enhanced, sources, sr, extended, False)
+
+
+def stoi_loss_rows(enhanced, sources, sr=16000, extended=False):
+    """The negated value per row, [rows] float32 on the device, differentiable as stoi_loss."""
+    return _stoi_loss(enhanced, sources, sr, extended, True)
+
+
+class StoiLoss(torch.nn.Module):
+    """stoi_loss(enhanced, sources, sr, extended) as a module that owns its buffers: one workspace per input shape, kept for the life of
+    the module (a captured graph refers to them), so feed it a bounded set of shapes -- training segments, not clips of every length."""
+
+    def __init__(self, sr=16000, extended=False):
+        super().__init__()
+        self.sr, self.extended = int(sr), bool(extended)
+        self._workspaces = {}
+
+    def workspace(self, shape, device):
+        """this module's buffers for inputs of `shape` on `device`; call it before a capture that records the loss"""
+        from . import metric
+        key = (tuple(shape), self.sr, str(metric._device(device)))
+        ws = self._workspaces.get(key)
+        if ws is None:
+            n = int(shape[-1])
+            rows = 1
+            for s in shape[:-1]:
+                rows *= int(s)
+            ws = StoiLossWorkspace(rows, n, self.sr, device)
+            if not torch.cuda.is_current_stream_capturing():
+                self._workspaces[key] = ws
+        return ws
+
+    def forward(self, enhanced, sources):
+        _stoi_loss_check(enhanced, sources)      # (before the workspace: a refusal allocates nothing)
+        return _stoi_loss(enhanced, sources, self.sr, self.extended, False, self.workspace(enhanced.shape, enhanced.device))
+
+    def extra_repr(self):
+        return f"sr={self.sr}, extended={self.extended}"

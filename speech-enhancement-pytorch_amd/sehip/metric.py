@@ -48,14 +48,14 @@ _stoi_tables = {}        # (p, q, device) -> (table [p][2 L / p + 1], p, q, L)
 _stoi_workspaces = {}    # (rows, n, sr, device) -> dict of buffers
 
 
-def stoi_ratio(sr):
+def stoi_ratio(sr, what="STOI"):
     """(p, q) = 10000 / sr reduced; refuses sr <= 0 and the ratios the resampler does not take"""
     if int(sr) != sr or sr <= 0:
-        raise SehipError(f"STOI: the sample rate must be a positive integer, got {sr}")
+        raise SehipError(f"{what}: the sample rate must be a positive integer, got {sr}")
     g = gcd(STOI_FS, int(sr))
     p, q = STOI_FS // g, int(sr) // g
     if p > STOI_MAX_P or q > STOI_MAX_Q:
-        raise SehipError(f"STOI: sample rate {sr} needs the ratio {p} / {q}; the resampler takes p <= {STOI_MAX_P}, q <= {STOI_MAX_Q}")
+        raise SehipError(f"{what}: sample rate {sr} needs the ratio {p} / {q}; the resampler takes p <= {STOI_MAX_P}, q <= {STOI_MAX_Q}")
     return p, q
 
 
@@ -99,33 +99,56 @@ def stoi_resample_table(sr, device="cpu"):
     return host
 
 
+def stoi_buffers(rows, n, sr, device, what="STOI"):
+    """Fresh buffers of the forward launches on `rows` pairs of n samples at sr; every refusal names `what` (sehip.loss.stoi_loss keeps
+    a set of its own, apart from the metric's cache)."""
+    device = _device(device)
+    p, q = stoi_ratio(sr, what)
+    n10 = n if p == q else stoi_out_len(n, sr)
+    if n10 < STOI_FRAME:
+        raise SehipError(f"{what}: {n} samples at {sr} Hz are {n10} samples at 10 kHz; one frame needs {STOI_FRAME}")
+    if not 1 <= rows <= STOI_MAX_ROWS:
+        raise SehipError(f"{what}: {rows} rows outside [1, {STOI_MAX_ROWS}]")
+    frames = lib().sehip_stoi_frames(n10)
+    if frames <= 0:
+        raise SehipError(f"{what}: {n10} samples at 10 kHz are more than the kernels index")
+    f32 = dict(device=device, dtype=torch.float32)
+    i32 = dict(device=device, dtype=torch.int32)
+    return dict(p=p, q=q, n10=n10, frames=frames,
+                table=None if p == q else stoi_resample_table(sr, device),
+                sig=None if p == q else torch.empty(2 * rows, n10, **f32),
+                level=torch.empty(rows, frames, **f32), kept=torch.empty(rows, **i32), src=torch.empty(rows, frames, **i32),
+                tob=torch.empty(2, rows, STOI_BANDS, max(frames - 1, 1), **f32),
+                partial=[torch.empty(rows, lib().sehip_stoi_segment_blocks(frames, ext), **f32) for ext in (0, 1)])
+
+
 def stoi_workspace(rows, n, sr, device):
     """The buffers of one STOI call on `rows` pairs of n samples at sr, cached per (rows, n, sr, device): a call allocates nothing but its
     result, so it can be captured into a graph."""
     device = _device(device)
     key = (rows, n, int(sr), str(device))
     ws = _stoi_workspaces.get(key)
-    if ws is not None:
-        return ws
-    p, q = stoi_ratio(sr)
-    n10 = n if p == q else stoi_out_len(n, sr)
-    if n10 < STOI_FRAME:
-        raise SehipError(f"STOI: {n} samples at {sr} Hz are {n10} samples at 10 kHz; one frame needs {STOI_FRAME}")
-    if not 1 <= rows <= STOI_MAX_ROWS:
-        raise SehipError(f"STOI: {rows} rows outside [1, {STOI_MAX_ROWS}]")
-    frames = lib().sehip_stoi_frames(n10)
-    if frames <= 0:
-        raise SehipError(f"STOI: {n10} samples at 10 kHz are more than the kernels index")
-    f32 = dict(device=device, dtype=torch.float32)
-    i32 = dict(device=device, dtype=torch.int32)
-    ws = dict(p=p, q=q, n10=n10, frames=frames,
-              table=None if p == q else stoi_resample_table(sr, device),
-              sig=None if p == q else torch.empty(2 * rows, n10, **f32),
-              level=torch.empty(rows, frames, **f32), kept=torch.empty(rows, **i32), src=torch.empty(rows, frames, **i32),
-              tob=torch.empty(2, rows, STOI_BANDS, max(frames - 1, 1), **f32),
-              partial=[torch.empty(rows, lib().sehip_stoi_segment_blocks(frames, ext), **f32) for ext in (0, 1)])
-    _stoi_workspaces[key] = ws
+    if ws is None:
+        ws = _stoi_workspaces[key] = stoi_buffers(rows, n, sr, device)
     return ws
+
+
+def stoi_forward(r, e, ws, extended, d, out):
+    """The forward launches on the contiguous float32 rows r (clean) and e (estimate) [rows, n] with the buffers `ws`: d [rows] and the
+    mean `out` are written; kept, src and tob (and, off 10 kHz, the resampled pair in sig) stay in `ws`."""
+    rows, n = r.shape
+    st, n10, frames = stream(), ws["n10"], ws["frames"]
+    if ws["sig"] is None:
+        clean, est = ptr(r), ptr(e)
+    else:
+        table, p, q, L = ws["table"]
+        call("sehip_stoi_resample", ptr(r), ptr(e), rows, n, ptr(table), p, q, L, ptr(ws["sig"]), st)
+        clean, est = ptr(ws["sig"]), ptr(ws["sig"][rows:])
+    call("sehip_stoi_levels", clean, rows, n10, ptr(ws["level"]), st)
+    call("sehip_stoi_select", ptr(ws["level"]), rows, frames, ptr(ws["kept"]), ptr(ws["src"]), st)
+    call("sehip_stoi_bands", clean, est, rows, n10, ptr(ws["kept"]), ptr(ws["src"]), ptr(ws["tob"]), st)
+    call("sehip_stoi_segments", ptr(ws["tob"]), ptr(ws["kept"]), rows, frames, int(bool(extended)),
+         ptr(ws["partial"][int(bool(extended))]), ptr(d), ptr(out), st)
 
 
 def _stoi_launch(reference, estimation, sr, extended, what):
@@ -148,18 +171,7 @@ def _stoi_launch(reference, estimation, sr, extended, what):
         e = estimation.reshape(rows, n).contiguous().float()
         d = torch.empty(rows, device=r.device, dtype=torch.float32)
         out = torch.empty((), device=r.device, dtype=torch.float32)
-        st, n10, frames = stream(), ws["n10"], ws["frames"]
-        if ws["sig"] is None:
-            clean, est = ptr(r), ptr(e)
-        else:
-            table, p, q, L = ws["table"]
-            call("sehip_stoi_resample", ptr(r), ptr(e), rows, n, ptr(table), p, q, L, ptr(ws["sig"]), st)
-            clean, est = ptr(ws["sig"]), ptr(ws["sig"][rows:])
-        call("sehip_stoi_levels", clean, rows, n10, ptr(ws["level"]), st)
-        call("sehip_stoi_select", ptr(ws["level"]), rows, frames, ptr(ws["kept"]), ptr(ws["src"]), st)
-        call("sehip_stoi_bands", clean, est, rows, n10, ptr(ws["kept"]), ptr(ws["src"]), ptr(ws["tob"]), st)
-        call("sehip_stoi_segments", ptr(ws["tob"]), ptr(ws["kept"]), rows, frames, int(bool(extended)),
-             ptr(ws["partial"][int(bool(extended))]), ptr(d), ptr(out), st)
+        stoi_forward(r, e, ws, extended, d, out)
     return d, out, ws
 
 

@@ -106,6 +106,15 @@ class DevicePrefetcher:
 class Solver(object):
     def __init__(self, config, model, optimizer=None, loss_function=None, train_dataloader=None,
                  validation_dataloader=None, test_dataloader=None, device="gpu", writer=None):
+        if _cfg(getattr(config, "optim", None), "loss", None) in ("stoi", "estoi"):
+            # the negated STOI / ESTOI is a loss on waveforms, one row per (batch, speaker, channel): refused from the configuration alone,
+            # before any device is touched
+            if config.model.name in STFT_MODELS:
+                raise SehipError(f"optim.loss '{config.optim.loss}' is taken on waveforms; model '{config.model.name}' returns spectra "
+                                 "(an STFT-domain model): train it with l1, mse or psa")
+            if _cfg(config.optim, "pit_apply", False):
+                raise SehipError(f"optim.loss '{config.optim.loss}' with optim.pit_apply is not built: the permutation-invariant losses "
+                                 "are si-sdr, l1 and mse")
         self.train_dataloader = train_dataloader
         self.validation_dataloader = validation_dataloader
         self.test_dataloader = test_dataloader
@@ -183,6 +192,8 @@ class Solver(object):
                              text_string=f"<pre>  \n{json.dumps(obj2dict(config), indent=4, sort_keys=False)}  \n</pre>",
                              global_step=1)
         self.config = config
+        if _cfg(getattr(config, "optim", None), "loss", None) in ("stoi", "estoi") and hasattr(loss_function, "sr"):
+            loss_function.sr = self._sample_rate()      # the rate the validation metric is taken at
         if config.solver.preloaded_model:
             self._preload_model()
         elif config.solver.resume:
@@ -463,6 +474,8 @@ class Solver(object):
         self.model.flat_grads
         self.model._grad_anchor(mixture.device)      # exists before the capture
         mix, src = mixture.clone(), sources.clone()
+        if hasattr(self.loss_function, "workspace"):
+            self.loss_function.workspace(src.shape, src.device)     # StoiLoss: its buffers exist before the capture
         if self._pit_applies(src):
             from . import loss as loss_module
             if self.loss_function in (loss_module.l1_loss, loss_module.mse_loss) and src.shape[1] <= loss_module.PIT_MAX_SPEAKERS:
