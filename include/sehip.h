@@ -1036,6 +1036,37 @@ int sehip_stoil_bands(const float* est, int rows, long len, const int* kept, con
 int sehip_stoil_compact(const float* fgrad, const int* kept, const int* src, int rows, long len, int* inv, float* out, void* stream);
 int sehip_stoil_resample_adj(const float* g, int rows, long n, const float* table, int p, int q, int L, float* out, void* stream);
 
+/* ---- the multi-resolution STFT loss (csrc/mrstft_loss.hip; sehip.loss.mrstft_loss): per resolution (n_fft, hop, win) the spectral
+ *      convergence ||Y - X||_F / ||Y||_F and the mean |log Y - log X| over the whole batch, of the magnitudes
+ *      M = sqrt(max(re^2 + im^2, 1e-7)) [rows][n_fft / 2 + 1][T = 1 + n / hop] of torch.stft (periodic hann of win centred in n_fft,
+ *      center=True, reflect padding, no division by win).  Accepted: n_fft a power of two in [64, 2048], 1 <= win <= n_fft,
+ *      1 <= hop <= win, n_fft / 2 < n <= 2^30, 1 <= rows <= 65535, 1 to 8 resolutions; everything else is refused before any launch.
+ *      window [n_fft] is the periodic hann of win with (n_fft - win) / 2 zeros in front and the rest behind.  No atomics, no readback,
+ *      fixed summation order, nothing allocated: every launch can be captured.
+ *      frames / blocks : T, and the workgroups (frame pairs) per row of one resolution; 0 for a bad argument
+ *      check           : res [n_res][3] = (n_fft, hop, win) in HOST memory; the refusals alone
+ *      forward         : partials [rows * blocks][3] = sum (Y - X)^2, sum Y^2, sum |log Y - log X| of each workgroup (X: enh, Y: src)
+ *      finalize        : partials of all resolutions back to back in the order of res; terms [n_res][2] = (sc, mag), loss [1] =
+ *                        (1 / n_res) sum (sc_weight sc + mag_weight mag), stats [n_res][2] = (1 / (||Y - X|| ||Y||) or 0 where
+ *                        ||Y - X|| = 0, 1 / cells) for backward
+ *      backward        : fgrad [rows][T][win] = the windowed gradient of every frame of enh; stats -> this resolution's pair, gout [1]
+ *                        the upstream gradient on the device, sc_scale = sc_weight / n_res, mag_scale = mag_weight / n_res.  A cell
+ *                        the forward clamped passes nothing, |.| at 0 has derivative 0
+ *      gather          : grad [rows][n] (+= if accumulate) the frames that cover sample s and its mirror images -s, 2 (n - 1) - s,
+ *                        frames ascending
+ *      magnitudes      : out [rows][n_fft / 2 + 1][T] = M(x) */
+long sehip_mrl_frames(long n, int hop);
+long sehip_mrl_blocks(long n, int hop);
+int sehip_mrl_check(int n_res, const int* res, int rows, long n);
+int sehip_mrl_forward(const float* enh, const float* src, int rows, long n, int n_fft, int hop, int win, const float* window,
+                      float* partials, void* stream);
+int sehip_mrl_finalize(const float* partials, int n_res, const int* res, int rows, long n, float sc_weight, float mag_weight,
+                       float* stats, float* terms, float* loss, void* stream);
+int sehip_mrl_backward(const float* enh, const float* src, int rows, long n, int n_fft, int hop, int win, const float* window,
+                       const float* stats, const float* gout, float sc_scale, float mag_scale, float* fgrad, void* stream);
+int sehip_mrl_gather(const float* fgrad, int rows, long n, int n_fft, int hop, int win, int accumulate, float* grad, void* stream);
+int sehip_mrl_magnitudes(const float* x, int rows, long n, int n_fft, int hop, int win, const float* window, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,7 @@ import torch
 import torch.distributed as dist
 
 from ._lib import SehipError
-from .loss import loss_sisdr, l1_loss, mse_loss, loss_phase_sensitive_spectral_approximation, StoiLoss
+from .loss import loss_sisdr, l1_loss, mse_loss, loss_phase_sensitive_spectral_approximation, StoiLoss, MRSTFTLoss, MRSTFT_RESOLUTIONS
 from .model.dccrn import DCCRN
 from .model.conv_tasnet import ConvTasNet
 from .model.dcunet import DCUnet
@@ -66,6 +66,9 @@ def get_loss_function(config, device="gpu"):
         return loss_phase_sensitive_spectral_approximation
     if config.loss in ("stoi", "estoi"):      # negated STOI / ESTOI of the waveforms; the Solver sets the sample rate (Solver._sample_rate)
         return StoiLoss(extended=config.loss == "estoi")
+    if config.loss in ("mrstft", "l1+mrstft"):    # multi-resolution STFT loss of the waveforms, with the waveform L1 for 'l1+mrstft'
+        res = getattr(config, "mrstft_resolutions", None)
+        return MRSTFTLoss(MRSTFT_RESOLUTIONS if res is None else [tuple(r) for r in res], wave_l1=1.0 if config.loss == "l1+mrstft" else 0.0)
     raise ValueError(f"Loss function {config.loss} cannot use...")
 
 

@@ -406,3 +406,182 @@ class StoiLoss(torch.nn.Module):
 
     def extra_repr(self):
         return f"sr={self.sr}, extended={self.extended}"
+
+
+# ---- the multi-resolution STFT loss (csrc/mrstft_loss.hip) -----------------------------------------------------------------------------
+MRSTFT_RESOLUTIONS = ((1024, 120, 600), (2048, 240, 1200), (512, 50, 240))     # (n_fft, hop, win_length)
+_mrstft_workspaces = {}       # (rows, n, resolutions, device) -> MRSTFTWorkspace of the functional form; an MRSTFTLoss module owns its own
+
+
+def _rows_of(shape):
+    rows = 1
+    for s in shape[:-1]:
+        rows *= int(s)
+    return rows
+
+
+class MRSTFTWorkspace:
+    """Every buffer of one mrstft_loss call on `rows` pairs of n samples: the windows, the per-workgroup partial sums of all resolutions,
+    the (sc, mag) terms, the loss, the two backward factors per resolution and the frame-gradient scratch (sized for the largest
+    resolution; the resolutions run one after another on one stream).  `generation` counts the forward passes: a backward pass whose
+    forward is no longer the latest one on these buffers is refused instead of differentiating the wrong call."""
+
+    def __init__(self, rows, n, resolutions, device):
+        from ._lib import lib
+        rows, n = int(rows), int(n)
+        self.res_host = ops.mrl_check(resolutions, rows, n, "mrstft_loss")          # refusals first: nothing is allocated for a bad shape
+        self.resolutions = tuple(tuple(r) for r in self.res_host.tolist())
+        self.rows, self.n = rows, n
+        f32 = dict(device=device, dtype=torch.float32)
+        self.windows = [ops.mrl_window(nf, w, device) for nf, _, w in self.resolutions]
+        self.blocks = [rows * lib().sehip_mrl_blocks(n, h) for _, h, _ in self.resolutions]
+        self.offsets = [sum(self.blocks[:r]) for r in range(len(self.blocks))]
+        self.partials = torch.empty(sum(self.blocks), 3, **f32)
+        self.terms = torch.empty(len(self.resolutions), 2, **f32)
+        self.stats = torch.empty(len(self.resolutions), 2, **f32)
+        self.loss = torch.empty((), **f32)
+        self.fgrad = torch.empty(max(rows * lib().sehip_mrl_frames(n, h) * w for _, h, w in self.resolutions), **f32)
+        self.generation = 0
+
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for t in [self.partials, self.terms, self.stats, self.loss, self.fgrad] + self.windows)
+
+
+def _mrstft_check(enhanced, sources, what="mrstft_loss"):
+    from ._lib import require_gpu
+    if not torch.is_tensor(enhanced) or not torch.is_tensor(sources):
+        raise SehipError(f"{what}: needs device tensors")
+    require_gpu(enhanced, what)
+    require_gpu(sources, what)
+    if enhanced.shape != sources.shape:
+        raise ValueError(f"{what}: shapes differ: {tuple(enhanced.shape)} vs {tuple(sources.shape)}")
+    if enhanced.dim() < 1 or enhanced.numel() == 0:
+        raise SehipError(f"{what}: empty input of shape {tuple(enhanced.shape)}")
+
+
+def _mrstft_key(shape, resolutions, device):
+    from . import metric
+    return (_rows_of(shape), int(shape[-1]), tuple(tuple(int(v) for v in r) for r in resolutions), str(metric._device(device)))
+
+
+def mrstft_loss_workspace(shape, resolutions=MRSTFT_RESOLUTIONS, device="cuda"):
+    """The cached workspace of the functional mrstft_loss / mrstft_terms for inputs of `shape` [..., T].  The loss fetches it itself; a
+    caller that records the loss into a hipGraph calls this BEFORE the capture begins, so that the recording allocates nothing but
+    the call's results."""
+    key = _mrstft_key(shape, resolutions, device)
+    ws = _mrstft_workspaces.get(key)
+    if ws is None:
+        ws = MRSTFTWorkspace(key[0], key[1], resolutions, device)
+        if not torch.cuda.is_current_stream_capturing():
+            _mrstft_workspaces[key] = ws       # (a buffer born inside a capture lives in that graph's pool: it serves that recording only)
+    return ws
+
+
+def _mrstft_forward(e, r, ws, sc_weight, mag_weight):
+    """the forward launches on rows [rows, n] fp32: one per resolution and the finalize; results stay in ws.loss / ws.terms / ws.stats"""
+    from ._lib import call, ptr, stream
+    st = stream()
+    for (nf, hop, win), window, off in zip(ws.resolutions, ws.windows, ws.offsets):
+        call("sehip_mrl_forward", ptr(e), ptr(r), ws.rows, ws.n, nf, hop, win, ptr(window), ptr(ws.partials[off:]), st)
+    call("sehip_mrl_finalize", ptr(ws.partials), len(ws.resolutions), ptr(ws.res_host), ws.rows, ws.n, float(sc_weight), float(mag_weight),
+         ptr(ws.stats), ptr(ws.terms), ptr(ws.loss), st)
+    ws.generation += 1
+
+
+class _MRSTFTLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, est, ref, ws, sc_weight, mag_weight):
+        e = est.detach().reshape(ws.rows, ws.n).contiguous().float()
+        r = ref.detach().reshape(ws.rows, ws.n).contiguous().float()
+        _mrstft_forward(e, r, ws, sc_weight, mag_weight)
+        ctx.ws, ctx.weights, ctx.generation, ctx.shape = ws, (float(sc_weight), float(mag_weight)), ws.generation, est.shape
+        ctx.save_for_backward(e, r)
+        return ws.loss.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        from ._lib import call, ptr, stream
+        ws = ctx.ws
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        if ws.generation != ctx.generation:
+            raise SehipError("mrstft_loss: another forward pass ran on this workspace before this one's backward pass; give each loss that "
+                             "is live at the same time an MRSTFTLoss module of its own")
+        e, r = ctx.saved_tensors
+        g = g.reshape(1).contiguous().float()
+        st = stream()
+        R = len(ws.resolutions)
+        grad = torch.empty(ws.rows, ws.n, device=g.device, dtype=torch.float32)
+        for i, ((nf, hop, win), window) in enumerate(zip(ws.resolutions, ws.windows)):
+            call("sehip_mrl_backward", ptr(e), ptr(r), ws.rows, ws.n, nf, hop, win, ptr(window), ptr(ws.stats[i]), ptr(g),
+                 ctx.weights[0] / R, ctx.weights[1] / R, ptr(ws.fgrad), st)
+            call("sehip_mrl_gather", ptr(ws.fgrad), ws.rows, ws.n, nf, hop, win, int(i > 0), ptr(grad), st)
+        return grad.view(ctx.shape), None, None, None, None
+
+
+def mrstft_loss(enhanced, sources, resolutions=MRSTFT_RESOLUTIONS, sc_weight=1.0, mag_weight=1.0, ws=None):
+    """The multi-resolution STFT loss (Yamamoto et al. 2020) of device tensors [..., T] of equal shape (rows = every axis but the last)
+    -> 0-dim float32 device tensor, differentiable with respect to `enhanced` (csrc/mrstft_loss.hip).  Per resolution
+    (n_fft, hop, win_length): S = torch.stft(row, n_fft, hop, win_length, hann_window(win_length), center=True, pad_mode='reflect'),
+    M = sqrt(max(re^2 + im^2, 1e-7)) [rows, n_fft / 2 + 1, 1 + T // hop] (torch's scaling: no division by win_length), X = M(enhanced),
+    Y = M(sources), sc = ||Y - X||_F / ||Y||_F and mag = mean |log Y - log X|, norms and mean over the whole batch;
+    loss = (1 / R) sum over the resolutions of sc_weight sc + mag_weight mag.  n_fft is a power of two in [64, 2048],
+    1 <= hop <= win_length <= n_fft, T > n_fft / 2, 1 to 8 resolutions; anything else raises SehipError before a launch.
+
+    The gradient's conventions: `sources` gets no gradient; a cell the forward clamped (re^2 + im^2 < 1e-7) passes nothing; |.| at
+    exactly 0 has derivative 0; ||Y - X|| = 0 gives an exactly zero gradient of the sc term, not a NaN.  No spectrum is stored (the
+    backward pass transforms both signals again), no readbacks and no atomics, every sum in a fixed order: two runs give the same bits,
+    and forward + backward can be captured into one graph (mrstft_loss_workspace(...) before the capture).  After the first call at a
+    shape nothing but the results is allocated.
+
+    Limit of this functional form: all calls at one (rows, T, resolutions, device) share one workspace, so only the LATEST forward pass
+    at a shape can be differentiated; the backward pass of an earlier one raises SehipError.  Give each loss that is live at the same
+    time an MRSTFTLoss module of its own (or pass `ws`, an MRSTFTWorkspace of the caller's own).  Workspaces stay allocated (a captured graph refers to their buffers): one per shape, each
+    with the frame-gradient scratch of win_length floats per frame and row of the largest resolution."""
+    _mrstft_check(enhanced, sources)
+    if ws is None:
+        ws = mrstft_loss_workspace(enhanced.shape, resolutions, enhanced.device)
+    return _MRSTFTLoss.apply(enhanced, sources, ws, float(sc_weight), float(mag_weight))
+
+
+def mrstft_terms(enhanced, sources, resolutions=MRSTFT_RESOLUTIONS, ws=None):
+    """[R, 2] float32 on the device: (sc, mag) of each resolution, from the forward launches of mrstft_loss.  Not differentiable."""
+    _mrstft_check(enhanced, sources, "mrstft_terms")
+    if ws is None:
+        ws = mrstft_loss_workspace(enhanced.shape, resolutions, enhanced.device)
+    e = enhanced.detach().reshape(ws.rows, ws.n).contiguous().float()
+    r = sources.detach().reshape(ws.rows, ws.n).contiguous().float()
+    _mrstft_forward(e, r, ws, 1.0, 1.0)
+    return ws.terms.clone()
+
+
+class MRSTFTLoss(torch.nn.Module):
+    """mrstft_loss(enhanced, sources, resolutions, sc_weight, mag_weight) as a module that owns its buffers: one workspace per input
+    shape, kept for the life of the module (a captured graph refers to them), so feed it a bounded set of shapes.  wave_l1 > 0 adds
+    wave_l1 * l1_loss(enhanced, sources), the waveform term of the Demucs denoiser recipe."""
+
+    def __init__(self, resolutions=MRSTFT_RESOLUTIONS, sc_weight=1.0, mag_weight=1.0, wave_l1=0.0):
+        super().__init__()
+        self.resolutions = tuple(tuple(int(v) for v in r) for r in resolutions)
+        self.sc_weight, self.mag_weight, self.wave_l1 = float(sc_weight), float(mag_weight), float(wave_l1)
+        self._workspaces = {}
+
+    def workspace(self, shape, device):
+        """this module's buffers for inputs of `shape` on `device`; call it before a capture that records the loss"""
+        key = _mrstft_key(shape, self.resolutions, device)
+        ws = self._workspaces.get(key)
+        if ws is None:
+            ws = MRSTFTWorkspace(key[0], key[1], self.resolutions, device)
+            if not torch.cuda.is_current_stream_capturing():
+                self._workspaces[key] = ws
+        return ws
+
+    def forward(self, enhanced, sources):
+        _mrstft_check(enhanced, sources)         # (before the workspace: a refusal allocates nothing)
+        loss = mrstft_loss(enhanced, sources, self.resolutions, self.sc_weight, self.mag_weight, self.workspace(enhanced.shape, enhanced.device))
+        if self.wave_l1 > 0.0:
+            loss = loss + self.wave_l1 * l1_loss(enhanced, sources)
+        return loss
+
+    def extra_repr(self):
+        return f"resolutions={self.resolutions}, sc_weight={self.sc_weight}, mag_weight={self.mag_weight}, wave_l1={self.wave_l1}"

@@ -228,3 +228,59 @@ def resample_frac(x, old_sr, new_sr):
     table, width, old, new = resample_kernels(old_sr, new_sr, x.device)
     call("sehip_resample_frac", ptr(xc), ptr(row_off), rows, ptr(table), old, new, width, ptr(out), ptr(out_off), stream())
     return out
+
+
+_mrl_windows = {}     # (n_fft, win_length, device) -> the periodic hann of win_length centred in n_fft zeros, fp32 [n_fft]
+
+
+def mrl_window(n_fft, win_length, device):
+    """torch.stft's window for (n_fft, win_length): hann_window(win_length) (periodic, rounded once from float64) behind
+    (n_fft - win_length) // 2 zeros, as a cached device table the kernels of csrc/mrstft_loss.hip read."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (int(n_fft), int(win_length), str(device))
+    w = _mrl_windows.get(key)
+    if w is None:
+        host = torch.zeros(int(n_fft), dtype=torch.float32)
+        lp = (int(n_fft) - int(win_length)) // 2
+        host[lp:lp + int(win_length)] = torch.hann_window(int(win_length), periodic=True, dtype=torch.float64).float()
+        w = host.to(device)
+        if not (device.type == "cuda" and torch.cuda.is_current_stream_capturing()):
+            _mrl_windows[key] = w
+    return w
+
+
+def mrl_check(resolutions, rows, n, what="mrstft"):
+    """The refusals of csrc/mrstft_loss.hip for `resolutions` ((n_fft, hop, win_length), ...) on rows x n samples, before any launch;
+    -> the resolutions as a host int32 tensor [R, 3]."""
+    try:
+        res = [tuple(int(v) for v in r) for r in resolutions]
+    except (TypeError, ValueError):
+        raise _lib.SehipError(f"{what}: resolutions must be (n_fft, hop, win_length) triples, got {resolutions!r}")
+    if any(len(r) != 3 for r in res):
+        raise _lib.SehipError(f"{what}: resolutions must be (n_fft, hop, win_length) triples, got {resolutions!r}")
+    host = torch.tensor(res, dtype=torch.int32).reshape(-1, 3)
+    status = _lib.lib().sehip_mrl_check(len(res), ptr(host) if res else None, int(rows), int(n))
+    if status != 0:
+        raise _lib.SehipError(f"{what}: {_lib.lib().sehip_last_error().decode()}")
+    return host
+
+
+def stft_magnitudes(x, n_fft, hop, win_length):
+    """M = sqrt(max(|torch.stft(x, n_fft, hop, win_length, hann_window(win_length), center=True, pad_mode='reflect')|^2, 1e-7)) for a
+    device tensor x [..., n] -> [rows, n_fft / 2 + 1, 1 + n // hop] fp32 (rows = every axis but the last): the magnitudes the
+    multi-resolution STFT loss is taken on, written out."""
+    if not torch.is_tensor(x):
+        raise _lib.SehipError("stft_magnitudes: needs a device tensor")
+    require_gpu(x, "stft_magnitudes")
+    if x.dim() < 1 or x.numel() == 0:
+        raise _lib.SehipError(f"stft_magnitudes: empty input of shape {tuple(x.shape)}")
+    n = int(x.shape[-1])
+    rows = x.numel() // n
+    mrl_check([(n_fft, hop, win_length)], rows, n, "stft_magnitudes")
+    xc = x.reshape(rows, n).contiguous().float()
+    out = torch.empty(rows, int(n_fft) // 2 + 1, 1 + n // int(hop), device=x.device, dtype=torch.float32)
+    call("sehip_mrl_magnitudes", ptr(xc), rows, n, int(n_fft), int(hop), int(win_length), ptr(mrl_window(n_fft, win_length, x.device)),
+         ptr(out), stream())
+    return out

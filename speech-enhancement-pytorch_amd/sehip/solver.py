@@ -115,6 +115,14 @@ class Solver(object):
             if _cfg(config.optim, "pit_apply", False):
                 raise SehipError(f"optim.loss '{config.optim.loss}' with optim.pit_apply is not built: the permutation-invariant losses "
                                  "are si-sdr, l1 and mse")
+        if _cfg(getattr(config, "optim", None), "loss", None) in ("mrstft", "l1+mrstft"):
+            # the multi-resolution STFT loss takes its own transforms of waveforms: refused from the configuration alone as well
+            if config.model.name in STFT_MODELS:
+                raise SehipError(f"optim.loss '{config.optim.loss}' is taken on waveforms; model '{config.model.name}' returns spectra "
+                                 "(an STFT-domain model): train it with l1, mse or psa")
+            if _cfg(config.optim, "pit_apply", False):
+                raise SehipError(f"optim.loss '{config.optim.loss}' with optim.pit_apply is not built: the permutation-invariant losses "
+                                 "are si-sdr, l1 and mse")
         self.train_dataloader = train_dataloader
         self.validation_dataloader = validation_dataloader
         self.test_dataloader = test_dataloader
