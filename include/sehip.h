@@ -1067,6 +1067,36 @@ int sehip_mrl_backward(const float* enh, const float* src, int rows, long n, int
 int sehip_mrl_gather(const float* fgrad, int rows, long n, int n_fft, int hop, int win, int accumulate, float* grad, void* stream);
 int sehip_mrl_magnitudes(const float* x, int rows, long n, int n_fft, int hop, int win, const float* window, float* out, void* stream);
 
+/* ---- the same loss under batch-level permutation-invariant training (sehip.loss.pit_mrstft_loss; src/loss.py:58-100): enh / src
+ *      [B][S][C][n], speakers on axis 1, 1 <= S <= 6, 1 <= B C <= 65535 and everything sehip_mrl_check accepts for B C rows.  Pair (i, j)
+ *      is estimated speaker i against target speaker j, its norms and mean over the B C rows.  No atomics, no readback, fixed summation
+ *      order, nothing allocated: every launch can be captured.
+ *      pair_blocks   : (host only) the floats of one resolution's partials, (2 S S + S) B C sehip_mrl_blocks(n, hop); 0 for a bad argument
+ *      pair_forward  : one workgroup per (b, c, frame pair) transforms each of the 2 S signals ONCE, holds the S targets' magnitudes and
+ *                      their logs in LDS (147,744 B at n_fft 2048, S 6) and writes partials [2 S S + S][B C blocks]: sum (Y_j - X_i)^2
+ *                      at i S + j, sum |log Y_j - log X_i| at S S + i S + j, sum Y_j^2 at 2 S S + j -- each with the bits of
+ *                      sehip_mrl_forward on (enh[:, i], src[:, j])
+ *      pair_select   : one workgroup; partials of all resolutions back to back in the order of res, each sum in the order of
+ *                      sehip_mrl_finalize (double); terms [n_res][S][S][2] = (sc, mag), matrix [S][S] = (1 / n_res) sum (sc_weight sc +
+ *                      mag_weight mag) + extra_weight extra[i][j] (extra [S][S] on the device or NULL: the pairloss of
+ *                      sehip_pit_pointwise_fwd for a waveform L1), perm [S] (perm[j] = the estimate matched with target j: the first
+ *                      minimum of sum_j matrix[perm[j]][j] in itertools.permutations order, strict '<' from 1e9, fp32, j ascending),
+ *                      loss [1] = (1 / S) sum_j matrix[perm[j]][j], stats [n_res][S][2] = the two factors of sehip_mrl_backward for target
+ *                      j and its matched estimate
+ *      pair_backward : sehip_mrl_backward with the pairing read from perm on the device: the estimate's row (b, i, c) against the
+ *                      target's row (b, j, c) with perm[j] == i and stats [S][2] of this resolution; sc_scale = sc_weight / (n_res S),
+ *                      mag_scale = mag_weight / (n_res S); fgrad [B S C][T][win] in the order of enh's rows, finished by
+ *                      sehip_mrl_gather on B S C rows */
+long sehip_mrl_pair_blocks(int B, int S, int C, long n, int hop);
+int sehip_mrl_pair_forward(const float* enh, const float* src, int B, int S, int C, long n, int n_fft, int hop, int win,
+                           const float* window, float* partials, void* stream);
+int sehip_mrl_pair_select(const float* partials, int n_res, const int* res, int B, int S, int C, long n, float sc_weight, float mag_weight,
+                          const float* extra /*or NULL*/, float extra_weight, float* terms, float* matrix, int* perm, float* loss,
+                          float* stats, void* stream);
+int sehip_mrl_pair_backward(const float* enh, const float* src, int B, int S, int C, long n, int n_fft, int hop, int win,
+                            const float* window, const float* stats, const int* perm, const float* gout, float sc_scale, float mag_scale,
+                            float* fgrad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

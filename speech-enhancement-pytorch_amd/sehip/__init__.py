@@ -11,6 +11,7 @@ from .audio import amplify_torch, convert_audio_channels  # noqa: F401
 from .metric import SI_SDR, STOI  # noqa: F401
 from .loss import StoiLoss, stoi_loss, stoi_loss_rows  # noqa: F401
 from .loss import MRSTFTLoss, mrstft_loss, mrstft_terms, mrstft_loss_workspace  # noqa: F401
+from .loss import PitMRSTFTLoss, pit_mrstft_loss, pit_mrstft_terms, pit_mrstft_workspace  # noqa: F401
 from .resample_stream import ResampleStreamer  # noqa: F401
 
 __version__ = "0.1.0"

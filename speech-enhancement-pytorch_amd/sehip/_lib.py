@@ -76,6 +76,10 @@ _PROTOS = {
     "sehip_mrl_backward": [P, P, I, L, I, I, I, P, P, P, F, F, P, P],
     "sehip_mrl_gather": [P, I, L, I, I, I, I, P, P],
     "sehip_mrl_magnitudes": [P, I, L, I, I, I, P, P, P],
+    "sehip_mrl_pair_blocks": [I, I, I, L, I],
+    "sehip_mrl_pair_forward": [P, P, I, I, I, L, I, I, I, P, P, P],
+    "sehip_mrl_pair_select": [P, I, P, I, I, I, L, F, F, P, F, P, P, P, P, P, P],
+    "sehip_mrl_pair_backward": [P, P, I, I, I, L, I, I, I, P, P, P, P, F, F, P, P],
     "sehip_sisnr_bwd": [P, P, P, P, I, I, P, P],
     "sehip_sisnr_pit_fwd": [P, P, I, I, I, I, P, P, P, P, P],
     "sehip_sisnr_pit_bwd": [P, P, P, P, P, I, I, I, I, P, P],
@@ -262,7 +266,7 @@ _PROTOS = {
     "sehip_unet_bn_bwd_reduce": [P, P, P, P, I, I, I, I, U, U, P, I, U, F, P, P],
     "sehip_unet_bn_bwd_apply": [P, P, P, P, P, I, I, I, I, U, U, P, I, U, F, P, P],
 }
-_RESTYPE = {"sehip_mrl_frames": C.c_long, "sehip_mrl_blocks": C.c_long, "sehip_resample_out_len": C.c_long,"sehip_stoi_out_len": C.c_long, "sehip_stoil_segment_floats": C.c_long, "sehip_ha_compressor_ws_doubles": C.c_long, "sehip_has_state_bytes": C.c_long, "sehip_rss_delay_frames": C.c_long, "sehip_rss_state_bytes": C.c_long, "sehip_rsm_sum_scratch_floats": C.c_long, "sehip_wun_bn_scratch_floats": C.c_long, "sehip_wun_enc0_wgrad_scratch_floats": C.c_long, "sehip_wun_out_bwd_scratch_floats": C.c_long,
+_RESTYPE = {"sehip_mrl_frames": C.c_long, "sehip_mrl_blocks": C.c_long, "sehip_mrl_pair_blocks": C.c_long, "sehip_resample_out_len": C.c_long,"sehip_stoi_out_len": C.c_long, "sehip_stoil_segment_floats": C.c_long, "sehip_ha_compressor_ws_doubles": C.c_long, "sehip_has_state_bytes": C.c_long, "sehip_rss_delay_frames": C.c_long, "sehip_rss_state_bytes": C.c_long, "sehip_rsm_sum_scratch_floats": C.c_long, "sehip_wun_bn_scratch_floats": C.c_long, "sehip_wun_enc0_wgrad_scratch_floats": C.c_long, "sehip_wun_out_bwd_scratch_floats": C.c_long,
             "sehip_lstm2_gran_bytes": C.c_long, "sehip_dmx_attn_bwd_scratch_floats": C.c_long, "sehip_ctn_codec_bwd_scratch_floats": C.c_long, "sehip_ctn_gln_bwd_scratch_floats": C.c_long, "sehip_ctn_cln_bwd_scratch_floats": C.c_long, "sehip_wgrad_group_bytes": C.c_long, "sehip_wgrad_dense_group_bytes": C.c_long, "sehip_cbn_scratch_floats": C.c_long, "sehip_rbn_scratch_floats": C.c_long, "sehip_dcunet_tail_scratch_floats": C.c_long, "sehip_event_create": C.c_void_p, "sehip_stream_create": C.c_void_p}
 
 

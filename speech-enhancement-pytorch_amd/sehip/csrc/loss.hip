@@ -9,6 +9,7 @@
 // exact residual energy -- the second read hits L2), the backward is one fused a*(x - alpha*s) + b*s pass whose three
 // row coefficients were produced by the forward.
 #include "common.h"
+#include "pit_perm.h"      // PIT_MAXS, pit_best_permutation
 
 #define EPS 1e-8f
 
@@ -174,7 +175,6 @@ extern "C" int sehip_sisnr_bwd(const float* est, const float* ref, const float* 
 //   rowstat [S*S][R] float4 (R = B*C rows per pair; pair index i*S + j), pairloss [S*S], perm [S] (perm[j] = estimated speaker
 //   matched with target j), loss [1]
 // ------------------------------------------------------------------------------------------------
-#define PIT_MAXS 6
 __global__ __launch_bounds__(256) void sisnr_pit_rows_kernel(const float* __restrict__ est, const float* __restrict__ ref, int B, int S,
                                                              int C, int n, float4* __restrict__ rowstat) {
     __shared__ float red[4];
@@ -206,31 +206,6 @@ __global__ __launch_bounds__(256) void sisnr_pit_rows_kernel(const float* __rest
         const float a = cc * (-2.f * q);
         const float bb = cc * (2.f * alpha * ss / ((ss + EPS) * (en + EPS)) + 2.f * q * es / (ss + EPS));
         rowstat[(size_t)pair * R + r] = make_float4(a, bb, l, alpha);
-    }
-}
-
-// The reference's walk over the permutations (src/loss.py:73-86): itertools.permutations(range(S)) order, strict '<' from
-// lmin = 1e9, the sum over j of m[perm[j]][j] taken in fp32 in the order j = 0 .. S-1.  m is the S x S pair matrix (row =
-// estimated speaker); best[j] = estimated speaker matched with target j.  One thread.
-__device__ void pit_best_permutation(const float* m, int S, int* best) {
-    int cur[PIT_MAXS];
-    for (int k = 0; k < S; ++k) cur[k] = best[k] = k;
-    float lmin = 1e9f;
-    for (;;) {
-        float l = 0.f;
-        for (int j = 0; j < S; ++j) l += m[cur[j] * S + j];
-        if (lmin > l) {
-            lmin = l;
-            for (int k = 0; k < S; ++k) best[k] = cur[k];
-        }
-        // next permutation in lexicographic order (the order of itertools.permutations(range(S)))
-        int k = S - 2;
-        while (k >= 0 && cur[k] > cur[k + 1]) --k;
-        if (k < 0) break;
-        int l2 = S - 1;
-        while (cur[l2] < cur[k]) --l2;
-        int t = cur[k]; cur[k] = cur[l2]; cur[l2] = t;
-        for (int a = k + 1, b = S - 1; a < b; ++a, --b) { t = cur[a]; cur[a] = cur[b]; cur[b] = t; }
     }
 }
 

@@ -17,9 +17,13 @@
 //   gather    : one thread per sample s adds, frames ascending, the stored frame gradients at padded positions s, -s and 2 (n - 1) - s
 //               (the adjoint of the reflect padding).
 //   frames<2> : the magnitudes of one signal written out, [rows][n_fft / 2 + 1][T] (sehip.ops.stft_magnitudes).
+//   pair_*    : the same loss under permutation-invariant training (sehip.loss.pit_mrstft_loss), further down: a forward that transforms
+//               each of the 2 S signals of a row group once and fills all S x S pairs, a select that adds the sums in finalize's order
+//               and picks the permutation, and frames<1> with the row pairing read from that permutation.
 // Conventions of the gradient: a cell the forward clamped (P < 1e-7) passes nothing; |.| at exactly 0 has derivative 0; ||Y - X|| = 0
 // gives an exactly zero sc gradient.
 #include "fft512.h"      // fft_detail::cossin_frac, the compile-time series behind g_fft_tw
+#include "pit_perm.h"    // PIT_MAXS, pit_best_permutation
 
 // The clean and the enhanced signal must come out of the same arithmetic (equal inputs -> equal bits -> sc exactly 0).  The compiler's
 // own choice of which multiply to fuse into which add follows the uses of a value, and those differ between the two signals (the backward
@@ -215,25 +219,30 @@ __device__ __forceinline__ float mrl_mag(float2 v, float& P) {
     return sqrtf(fmaxf(P, MRL_CLAMP));
 }
 
+extern __shared__ __align__(16) float2 mrl_lds[];
+
+// The work of one workgroup of frames<MODE>: the enhanced frames of `row` against the clean frames of `src_row`, with the backward factors
+// `stats` of that pairing (<1>); partial sums and gradients are stored under `row`.  frames<0 .. 2> pair a row with itself; the backward
+// pass of the permutation-invariant loss reads the pairing from the permutation.
 template <int MODE, int LG>
-__global__ __launch_bounds__(MRL_THREADS) void mrl_frames_kernel(MrlFrames a) {
-    extern __shared__ float2 mrl_lds[];          // twiddles [N]; <0>, <1>: enhanced pair [N], clean pair [N], 16 floats   <2>: one pair [N]
+__device__ __forceinline__ void mrl_frames_body(const MrlFrames& a, int row, int src_row, const float* __restrict__ stats) {
+    // twiddles [N]; <0>, <1>: enhanced pair [N], clean pair [N], 16 floats   <2>: one pair [N]
     constexpr int N = 1 << LG;
-    const int row = blockIdx.y, t0 = 2 * blockIdx.x, tid = threadIdx.x;
+    const int t0 = 2 * blockIdx.x, tid = threadIdx.x;
     const bool two = t0 + 1 < a.T;
     MrlCs* tw = (MrlCs*)mrl_lds;
     float2* zx = mrl_lds + N;
     float2* zy = mrl_lds + 2 * N;
     for (int j = tid; j < N; j += MRL_THREADS) tw[j] = g_mrl_tw.w[j];
     mrl_load<N>(a.enh + (size_t)row * a.n, a, t0, zx);
-    if (MODE != 2) mrl_load<N>(a.src + (size_t)row * a.n, a, t0, zy);
+    if (MODE != 2) mrl_load<N>(a.src + (size_t)src_row * a.n, a, t0, zy);
     mrl_fft_dif<N, LG, MODE == 2 ? 1 : 2>(zx, tw);
 
     float sA = 0.f, sB = 0.f, sC = 0.f, ksc = 0.f, kmag = 0.f;
     if (MODE == 1) {
         const float g = a.gout[0];
-        ksc = g * a.ksc * a.stats[0];
-        kmag = g * a.kmag * a.stats[1];
+        ksc = g * a.ksc * stats[0];
+        kmag = g * a.kmag * stats[1];
     }
     for (int k = tid; k <= N / 2; k += MRL_THREADS) {
         const int p = (int)(__brev((unsigned)k) >> (32 - LG)), q = (int)(__brev((unsigned)((N - k) & (N - 1))) >> (32 - LG));
@@ -300,6 +309,11 @@ __global__ __launch_bounds__(MRL_THREADS) void mrl_frames_kernel(MrlFrames a) {
             if (two) o[a.win + u] = w * v.y;
         }
     }
+}
+
+template <int MODE, int LG>
+__global__ __launch_bounds__(MRL_THREADS) void mrl_frames_kernel(MrlFrames a) {
+    mrl_frames_body<MODE, LG>(a, blockIdx.y, blockIdx.y, a.stats);
 }
 
 struct MrlFinal {
@@ -411,6 +425,237 @@ MrlFrames mrl_args(const float* enh, const float* src, const float* window, long
     a.win = win;
     return a;
 }
+
+// ---- the permutation-invariant form (sehip.loss.pit_mrstft_loss): enh / src [B][S][C][n], speakers on axis 1 -----------------------------
+// Pair (i, j) is estimated speaker i against target speaker j, its norms and mean taken over the B C rows.  A pair needs the magnitudes of
+// two signals out of 2 S, so a workgroup transforms each of them once and fills every pair from there.
+struct MrlPair {
+    MrlFrames f;           // f.enh / f.src: [B][S][C][n]; f.partials: the sums of one resolution, [2 S S + S][nblk]
+    int S, C;
+    long nblk;             // B C workgroups of frame pairs: index (b C + c) pairs + pair, the order of frames<0> on the slices
+};
+constexpr int MRLP_RED = 2 * PIT_MAXS;      // partial sums of one signal: sum (Y_j - X)^2 and sum |log Y_j - log X| for every target j
+
+// the workgroup's sum of each of vals[v], v = t PIT_MAXS + j with j < S, in the order of frames<0> (wave_sum, then the four waves in
+// index order), stored at out[(base[t] + j) nblk]
+__device__ __forceinline__ void mrlp_reduce(const float (&vals)[MRLP_RED], int kinds, int S, float* red, float* out, int base0, int base1,
+                                            long nblk) {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int v = 0; v < MRLP_RED; ++v) {
+        if (v / PIT_MAXS < kinds && v % PIT_MAXS < S) {
+            const float x = wave_sum(vals[v]);
+            if ((tid & 63) == 0) red[(tid >> 6) * MRLP_RED + v] = x;
+        }
+    }
+    __syncthreads();
+    if (tid < MRLP_RED && tid / PIT_MAXS < kinds && tid % PIT_MAXS < S) {
+        const int at = (tid < PIT_MAXS ? base0 : base1) + tid % PIT_MAXS;
+        out[(size_t)at * nblk] = ((red[tid] + red[MRLP_RED + tid]) + red[2 * MRLP_RED + tid]) + red[3 * MRLP_RED + tid];
+    }
+    __syncthreads();                                  // (red is written again by the next signal)
+}
+
+// signals per transform pass: two side by side where one alone would leave threads without a butterfly (n_fft / 4 < 256), one from 1024
+// on -- the same arithmetic, and 8 n_fft bytes of LDS less, which is a workgroup more per CU at 1024 and at 2048 with two speakers
+constexpr int mrlp_nb(int n_fft) { return n_fft >= 1024 ? 1 : 2; }
+
+// One workgroup per (b, c, frame pair t0, t0 + 1).  The 2 S signals of that (b, c) -- targets first -- go through the transform of
+// frames<0> mrlp_nb at a time.  A target leaves (Y(t0), Y(t0 + 1), log Y(t0), log Y(t0 + 1)) per bin in LDS and its sum Y^2; an estimate is
+// taken against every target in LDS as it comes out of the transform.  Thread, bin and frame order of every sum are those of frames<0>
+// on (enh[:, i], src[:, j]), so the partial sums carry the same bits.  A thread reads back only the bins it wrote itself.
+// LDS: twiddles [N], the signals in the transform [mrlp_nb N] (float2), targets [S][N / 2 + 1] (float4), 4 x 12 floats: 131,360 B at
+// N = 2048, S = 6; 65,760 B at N = 2048, S = 2.
+template <int LG>
+__global__ __launch_bounds__(MRL_THREADS) void mrl_pair_fwd_kernel(MrlPair a) {
+    constexpr int N = 1 << LG, BINS = N / 2 + 1, NB = mrlp_nb(N);
+    const MrlFrames& f = a.f;
+    const int S = a.S, row = blockIdx.y, b = row / a.C, c = row - b * a.C, t0 = 2 * blockIdx.x, tid = threadIdx.x;
+    const bool two = t0 + 1 < f.T;
+    MrlCs* tw = (MrlCs*)mrl_lds;
+    float2* z = mrl_lds + N;
+    float4* ymag = (float4*)(mrl_lds + (1 + NB) * N);
+    float* red = (float*)(ymag + (size_t)S * BINS);
+    float* out = f.partials + (size_t)row * gridDim.x + blockIdx.x;
+    for (int j = tid; j < N; j += MRL_THREADS) tw[j] = g_mrl_tw.w[j];
+    for (int g0 = 0; g0 < 2 * S; g0 += NB) {
+        if (g0) __syncthreads();                      // (every read of the signals before)
+#pragma unroll
+        for (int s = 0; s < NB; ++s) {
+            const int g = g0 + s, spk = g < S ? g : g - S;
+            mrl_load<N>((g < S ? f.src : f.enh) + (((size_t)b * S + spk) * a.C + c) * f.n, f, t0, z + s * N);
+        }
+        mrl_fft_dif<N, LG, NB>(z, tw);
+#pragma unroll
+        for (int s = 0; s < NB; ++s) {
+            const int g = g0 + s;
+            const float2* zs = z + s * N;
+            float vals[MRLP_RED];
+#pragma unroll
+            for (int v = 0; v < MRLP_RED; ++v) vals[v] = 0.f;
+            if (g < S) {
+                float4* ym = ymag + (size_t)g * BINS;
+                for (int k = tid; k <= N / 2; k += MRL_THREADS) {
+                    const int p = (int)(__brev((unsigned)k) >> (32 - LG)), q = (int)(__brev((unsigned)((N - k) & (N - 1))) >> (32 - LG));
+                    float2 Y[2];
+                    float P;
+                    mrl_split(zs[p], zs[q], Y[0], Y[1]);
+                    const float M0 = mrl_mag(Y[0], P), M1 = mrl_mag(Y[1], P);
+                    ym[k] = make_float4(M0, M1, logf(M0), logf(M1));
+                    vals[0] = fmaf(M0, M0, vals[0]);
+                    if (two) vals[0] = fmaf(M1, M1, vals[0]);
+                }
+                mrlp_reduce(vals, 1, 1, red, out, 2 * S * S + g, 0, a.nblk);
+            } else {
+                for (int k = tid; k <= N / 2; k += MRL_THREADS) {
+                    const int p = (int)(__brev((unsigned)k) >> (32 - LG)), q = (int)(__brev((unsigned)((N - k) & (N - 1))) >> (32 - LG));
+                    float2 X[2];
+                    float P;
+                    mrl_split(zs[p], zs[q], X[0], X[1]);
+                    const float M0 = mrl_mag(X[0], P), M1 = mrl_mag(X[1], P);
+                    const float L0 = logf(M0), L1 = logf(M1);
+#pragma unroll
+                    for (int j = 0; j < PIT_MAXS; ++j) {
+                        if (j < S) {
+                            const float4 y = ymag[(size_t)j * BINS + k];
+                            const float d0 = y.x - M0, l0 = y.z - L0;
+                            vals[j] = fmaf(d0, d0, vals[j]);
+                            vals[PIT_MAXS + j] += fabsf(l0);
+                            if (two) {
+                                const float d1 = y.y - M1, l1 = y.w - L1;
+                                vals[j] = fmaf(d1, d1, vals[j]);
+                                vals[PIT_MAXS + j] += fabsf(l1);
+                            }
+                        }
+                    }
+                }
+                mrlp_reduce(vals, 2, S, red, out, (g - S) * S, S * S + (g - S) * S, a.nblk);
+            }
+        }
+    }
+}
+
+struct MrlPairFinal {
+    int n_res, S;
+    long off[MRL_MAX_RES];                         // floats in front of resolution r's sums
+    int nblk[MRL_MAX_RES];
+    double cells[MRL_MAX_RES];                     // B C (n_fft / 2 + 1) T
+    float scw, magw, extra_weight;
+};
+
+// One workgroup.  Every sum is taken as finalize takes it -- thread q of 1024 adds the records q, q + 1024, .., the xor tree of a wave, the
+// 16 waves in index order, all in double -- so sc, mag carry finalize's bits; a thread carries MRLP_VC sums at a time to keep that many
+// loads of a trip in flight (one workgroup reads every record: the launch is bound by the latency of those loads).  Then
+// matrix[i][j] = (1 / R) sum_r (scw sc + magw mag) (+ extra_weight extra[i][j]), the walk over the permutations, the loss
+// (1 / S) sum_j matrix[perm[j]][j] in fp32 and, per (resolution, target j), the backward factors of the matched pair.
+constexpr int MRLP_VC = 8;
+__global__ __launch_bounds__(MRL_FIN_THREADS) void mrl_pair_select_kernel(const float* __restrict__ partials, MrlPairFinal f,
+                                                                          const float* __restrict__ extra, float* __restrict__ terms,
+                                                                          float* __restrict__ matrix, int* __restrict__ perm,
+                                                                          float* __restrict__ loss, float* __restrict__ stats) {
+    constexpr int SS_MAX = PIT_MAXS * PIT_MAXS, NV_MAX = 2 * SS_MAX + PIT_MAXS, WAVES = MRL_FIN_THREADS / 64;
+    __shared__ double red[NV_MAX][WAVES];
+    __shared__ double sums[NV_MAX];
+    __shared__ float inv[MRL_MAX_RES][SS_MAX];
+    __shared__ float m[SS_MAX];
+    const int tid = threadIdx.x, S = f.S, SS = S * S, NV = 2 * SS + S;
+    double total = 0.0;                            // thread i S + j: pair (i, j)
+    for (int r = 0; r < f.n_res; ++r) {
+        const int nblk = f.nblk[r];
+        for (int v0 = 0; v0 < NV; v0 += MRLP_VC) {
+            const float* p = partials + f.off[r] + (size_t)v0 * nblk;
+            double acc[MRLP_VC];
+#pragma unroll
+            for (int u = 0; u < MRLP_VC; ++u) acc[u] = 0.0;
+#pragma unroll 2
+            for (int i = tid; i < nblk; i += MRL_FIN_THREADS) {
+#pragma unroll
+                for (int u = 0; u < MRLP_VC; ++u)
+                    if (v0 + u < NV) acc[u] += (double)p[(size_t)u * nblk + i];
+            }
+#pragma unroll
+            for (int u = 0; u < MRLP_VC; ++u) {
+                if (v0 + u < NV) {
+                    const double x = wave_sum_d(acc[u]);
+                    if ((tid & 63) == 0) red[v0 + u][tid >> 6] = x;
+                }
+            }
+        }
+        __syncthreads();
+        if (tid < NV) {
+            double x = red[tid][0];
+            for (int w = 1; w < WAVES; ++w) x += red[tid][w];
+            sums[tid] = x;
+        }
+        __syncthreads();
+        if (tid < SS) {
+            const double v0 = sums[tid], v1 = sums[2 * SS + tid % S], v2 = sums[SS + tid];
+            const double na = sqrt(v0), nb = sqrt(v1);
+            const double sc = na / nb, mag = v2 / f.cells[r];
+            terms[((size_t)r * SS + tid) * 2] = (float)sc;
+            terms[((size_t)r * SS + tid) * 2 + 1] = (float)mag;
+            inv[r][tid] = v0 > 0.0 ? (float)(1.0 / (na * nb)) : 0.f;
+            total += (double)f.scw * sc + (double)f.magw * mag;
+        }
+        __syncthreads();                           // (sums is written again by the next resolution)
+    }
+    if (tid < SS) {
+        float v = (float)(total / f.n_res);
+        if (extra) v = v + f.extra_weight * extra[tid];
+        m[tid] = v;
+        matrix[tid] = v;
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    int best[PIT_MAXS];
+    pit_best_permutation(m, S, best);
+    float tot = 0.f;
+    for (int j = 0; j < S; ++j) {
+        perm[j] = best[j];
+        tot += m[best[j] * S + j];
+    }
+    loss[0] = tot / S;
+    for (int r = 0; r < f.n_res; ++r)
+        for (int j = 0; j < S; ++j) {
+            stats[((size_t)r * S + j) * 2] = inv[r][best[j] * S + j];
+            stats[((size_t)r * S + j) * 2 + 1] = (float)(1.0 / f.cells[r]);
+        }
+}
+
+// frames<1> with the pairing read from the permutation: grid (frame pairs, B C, S); estimated speaker i = blockIdx.z goes against the
+// target j with perm[j] == i and that target's factors stats[j][2]; fgrad in the order of the estimate's rows, (b S + i) C + c
+template <int LG>
+__global__ __launch_bounds__(MRL_THREADS) void mrl_pair_bwd_kernel(MrlFrames a, const int* __restrict__ perm, int S, int C) {
+    const int i = blockIdx.z, b = blockIdx.y / C, c = blockIdx.y - b * C;
+    int j = 0;
+    for (int k = 0; k < S; ++k)
+        if (perm[k] == i) j = k;
+    mrl_frames_body<1, LG>(a, (b * S + i) * C + c, (b * S + j) * C + c, a.stats + 2 * j);
+}
+
+int mrl_pair_check(const char* who, int B, int S, int C, long n, int n_fft, int hop, int win) {
+    SEHIP_REQUIRE(S >= 1 && S <= PIT_MAXS, "%s: S=%d speakers outside [1, %d]", who, S, PIT_MAXS);
+    SEHIP_REQUIRE(B >= 1 && C >= 1 && (long)B * C <= MRL_MAX_ROWS, "%s: rows=%ld (B=%d times C=%d) outside [1, %d]", who, (long)B * C, B, C,
+                  MRL_MAX_ROWS);
+    return mrl_check(who, B * C, n, n_fft, hop, win);
+}
+
+size_t mrl_pair_lds(int S, int n_fft) {
+    return (size_t)(1 + mrlp_nb(n_fft)) * n_fft * sizeof(float2) + (size_t)S * (n_fft / 2 + 1) * sizeof(float4) + 4 * MRLP_RED * sizeof(float);
+}
+
+template <int LG>
+int mrl_pair_launch_fwd(const MrlPair& a, const dim3& grid, size_t lds, hipStream_t st) {
+    static bool attr = false;                      // a workgroup with six targets at 2048 takes more than the 64 KB a launch gets unasked
+    if (!attr) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mrl_pair_fwd_kernel<LG>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        SEHIP_REQUIRE(e == hipSuccess, "mrl_pair_forward: hipFuncSetAttribute: %s", hipGetErrorString(e));
+        attr = true;
+    }
+    mrl_pair_fwd_kernel<LG><<<grid, MRL_THREADS, lds, st>>>(a);
+    return 0;
+}
 }  // namespace
 
 extern "C" long sehip_mrl_frames(long n, int hop) { return hop >= 1 && n >= 1 ? 1 + n / hop : 0; }
@@ -495,5 +740,94 @@ extern "C" int sehip_mrl_magnitudes(const float* x, int rows, long n, int n_fft,
     mrl_launch<2>(a, rows, (hipStream_t)stream);
     SEHIP_CHECK_LAUNCH("mrl_magnitudes");
     sehip_note_kernel("mrl_magnitudes n_fft=%d T=%d", n_fft, a.T);
+    return 0;
+}
+
+// ---- the permutation-invariant form -------------------------------------------------------------------------------------------------------
+extern "C" long sehip_mrl_pair_blocks(int B, int S, int C, long n, int hop) {
+    if (B < 1 || C < 1 || S < 1 || S > PIT_MAXS || (long)B * C > MRL_MAX_ROWS) return 0;
+    return (long)(2 * S * S + S) * B * C * sehip_mrl_blocks(n, hop);
+}
+
+extern "C" int sehip_mrl_pair_forward(const float* enh, const float* src, int B, int S, int C, long n, int n_fft, int hop, int win,
+                                      const float* window, float* partials, void* stream) {
+    if (int e = mrl_pair_check("mrl_pair_forward", B, S, C, n, n_fft, hop, win)) return e;
+    SEHIP_REQUIRE(enh && src && window && partials, "mrl_pair_forward: null pointer");
+    MrlPair a{};
+    a.f = mrl_args(enh, src, window, n, n_fft, hop, win);
+    a.f.partials = partials;
+    a.S = S;
+    a.C = C;
+    const dim3 grid((a.f.T + 1) / 2, B * C);
+    a.nblk = (long)grid.x * grid.y;
+    const size_t lds = mrl_pair_lds(S, n_fft);
+    hipStream_t st = (hipStream_t)stream;
+    int e = 0;
+    switch (n_fft) {
+        case 64: e = mrl_pair_launch_fwd<6>(a, grid, lds, st); break;
+        case 128: e = mrl_pair_launch_fwd<7>(a, grid, lds, st); break;
+        case 256: e = mrl_pair_launch_fwd<8>(a, grid, lds, st); break;
+        case 512: e = mrl_pair_launch_fwd<9>(a, grid, lds, st); break;
+        case 1024: e = mrl_pair_launch_fwd<10>(a, grid, lds, st); break;
+        default: e = mrl_pair_launch_fwd<11>(a, grid, lds, st); break;      // 2048 (mrl_check has run)
+    }
+    if (e) return e;
+    SEHIP_CHECK_LAUNCH("mrl_pair_forward");
+    sehip_note_kernel("mrl_pair_forward n_fft=%d T=%d S=%d lds=%zu", n_fft, a.f.T, S, lds);
+    return 0;
+}
+
+extern "C" int sehip_mrl_pair_select(const float* partials, int n_res, const int* res, int B, int S, int C, long n, float sc_weight,
+                                     float mag_weight, const float* extra, float extra_weight, float* terms, float* matrix, int* perm,
+                                     float* loss, float* stats, void* stream) {
+    SEHIP_REQUIRE(S >= 1 && S <= PIT_MAXS, "mrl_pair_select: S=%d speakers outside [1, %d]", S, PIT_MAXS);
+    SEHIP_REQUIRE(B >= 1 && C >= 1 && (long)B * C <= MRL_MAX_ROWS, "mrl_pair_select: rows=%ld (B=%d times C=%d) outside [1, %d]",
+                  (long)B * C, B, C, MRL_MAX_ROWS);
+    if (int e = sehip_mrl_check(n_res, res, B * C, n)) return e;
+    SEHIP_REQUIRE(partials && terms && matrix && perm && loss && stats, "mrl_pair_select: null pointer");
+    MrlPairFinal f{};
+    f.n_res = n_res;
+    f.S = S;
+    f.scw = sc_weight;
+    f.magw = mag_weight;
+    f.extra_weight = extra_weight;
+    long off = 0;
+    for (int r = 0; r < n_res; ++r) {
+        const long nblk = (long)B * C * sehip_mrl_blocks(n, res[3 * r + 1]);
+        SEHIP_REQUIRE(nblk <= (1L << 30), "mrl_pair_select: %ld workgroups of one resolution are more than 2^30", nblk);
+        f.off[r] = off;
+        f.nblk[r] = (int)nblk;
+        f.cells[r] = (double)B * C * (res[3 * r] / 2 + 1) * (double)sehip_mrl_frames(n, res[3 * r + 1]);
+        off += (long)(2 * S * S + S) * nblk;
+    }
+    mrl_pair_select_kernel<<<1, MRL_FIN_THREADS, 0, (hipStream_t)stream>>>(partials, f, extra, terms, matrix, perm, loss, stats);
+    SEHIP_CHECK_LAUNCH("mrl_pair_select");
+    return 0;
+}
+
+extern "C" int sehip_mrl_pair_backward(const float* enh, const float* src, int B, int S, int C, long n, int n_fft, int hop, int win,
+                                       const float* window, const float* stats, const int* perm, const float* gout, float sc_scale,
+                                       float mag_scale, float* fgrad, void* stream) {
+    if (int e = mrl_pair_check("mrl_pair_backward", B, S, C, n, n_fft, hop, win)) return e;
+    SEHIP_REQUIRE(enh && src && window && stats && perm && gout && fgrad, "mrl_pair_backward: null pointer");
+    MrlFrames a = mrl_args(enh, src, window, n, n_fft, hop, win);
+    a.stats = stats;
+    a.gout = gout;
+    a.ksc = sc_scale;
+    a.kmag = mag_scale;
+    a.out = fgrad;
+    const dim3 grid((a.T + 1) / 2, B * C, S);
+    const size_t lds = (size_t)3 * n_fft * sizeof(float2);
+    hipStream_t st = (hipStream_t)stream;
+    switch (n_fft) {
+        case 64: mrl_pair_bwd_kernel<6><<<grid, MRL_THREADS, lds, st>>>(a, perm, S, C); break;
+        case 128: mrl_pair_bwd_kernel<7><<<grid, MRL_THREADS, lds, st>>>(a, perm, S, C); break;
+        case 256: mrl_pair_bwd_kernel<8><<<grid, MRL_THREADS, lds, st>>>(a, perm, S, C); break;
+        case 512: mrl_pair_bwd_kernel<9><<<grid, MRL_THREADS, lds, st>>>(a, perm, S, C); break;
+        case 1024: mrl_pair_bwd_kernel<10><<<grid, MRL_THREADS, lds, st>>>(a, perm, S, C); break;
+        default: mrl_pair_bwd_kernel<11><<<grid, MRL_THREADS, lds, st>>>(a, perm, S, C); break;
+    }
+    SEHIP_CHECK_LAUNCH("mrl_pair_backward");
+    sehip_note_kernel("mrl_pair_backward n_fft=%d T=%d S=%d", n_fft, a.T, S);
     return 0;
 }

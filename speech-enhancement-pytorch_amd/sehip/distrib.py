@@ -9,7 +9,7 @@ import torch
 import torch.distributed as dist
 
 from ._lib import SehipError
-from .loss import loss_sisdr, l1_loss, mse_loss, loss_phase_sensitive_spectral_approximation, StoiLoss, MRSTFTLoss, MRSTFT_RESOLUTIONS
+from .loss import loss_sisdr, l1_loss, mse_loss, loss_phase_sensitive_spectral_approximation, StoiLoss, MRSTFTLoss, PitMRSTFTLoss, MRSTFT_RESOLUTIONS
 from .model.dccrn import DCCRN
 from .model.conv_tasnet import ConvTasNet
 from .model.dcunet import DCUnet
@@ -69,6 +69,10 @@ def get_loss_function(config, device="gpu"):
     if config.loss in ("mrstft", "l1+mrstft"):    # multi-resolution STFT loss of the waveforms, with the waveform L1 for 'l1+mrstft'
         res = getattr(config, "mrstft_resolutions", None)
         return MRSTFTLoss(MRSTFT_RESOLUTIONS if res is None else [tuple(r) for r in res], wave_l1=1.0 if config.loss == "l1+mrstft" else 0.0)
+    if config.loss in ("pit-mrstft", "pit-l1+mrstft"):    # the same under batch-level PIT, for models that return [batch, speakers, ...]
+        res = getattr(config, "mrstft_resolutions", None)
+        return PitMRSTFTLoss(MRSTFT_RESOLUTIONS if res is None else [tuple(r) for r in res],
+                             wave_l1=1.0 if config.loss == "pit-l1+mrstft" else 0.0)
     raise ValueError(f"Loss function {config.loss} cannot use...")
 
 

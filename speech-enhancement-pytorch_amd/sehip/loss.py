@@ -149,8 +149,9 @@ def pit_loss_pointwise(enhance, target, mode, return_comb=False):
 
 
 def pit_loss(enhance, target, loss_function, return_comb=False):
-    """The same for any loss function of this module.  si-sdr, l1 and mse run fused on the device without a host round trip (l1 / mse
-    for up to 6 speakers on the GPU: pit_loss_pointwise; return_comb then gives the reference's list of (ienhance, itarget) pairs,
+    """The same for any loss function of this module.  si-sdr, l1, mse and the multi-resolution STFT loss run fused on the device
+    without a host round trip (l1 / mse and mrstft_loss / an MRSTFTLoss module for up to 6 speakers on the GPU: pit_loss_pointwise,
+    pit_mrstft_loss; return_comb then gives the reference's list of (ienhance, itarget) pairs,
     built from the device permutation with one readback on that opt-in path only).  Any other loss function, or more than 6
     speakers, evaluates the S x S pair matrix with S*S small launches and reads it back once to pick the permutation
     (src/loss.py:67-86).  `psa` is not a PIT loss: the reference's own PIT raises for it (src/loss.py:95 calls the three-argument loss
@@ -160,6 +161,20 @@ def pit_loss(enhance, target, loss_function, return_comb=False):
     if (loss_function is l1_loss or loss_function is mse_loss) and enhance.shape == target.shape and enhance.dim() >= 2 and \
             1 <= enhance.shape[1] <= PIT_MAX_SPEAKERS and enhance.is_cuda and enhance.numel() > 0:
         res = pit_loss_pointwise(enhance, target, 0 if loss_function is l1_loss else 1, return_comb)
+        if not return_comb:
+            return res
+        return res[0], [(i, j) for j, i in enumerate(res[1].cpu().tolist())]
+    if loss_function is mrstft_loss or isinstance(loss_function, MRSTFTLoss):
+        # every signal transformed once, the permutation picked on the device (pit_mrstft_loss); an MRSTFTLoss module brings its
+        # resolutions, weights and wave_l1 and keeps the permutation-invariant form's workspaces with it
+        if loss_function is mrstft_loss:
+            res = pit_mrstft_loss(enhance, target, return_comb=return_comb)
+        else:
+            pit = loss_function.__dict__.get("_pit")
+            if pit is None:                        # (through __dict__: a helper of this call path, not a registered submodule)
+                pit = loss_function.__dict__["_pit"] = PitMRSTFTLoss(loss_function.resolutions, loss_function.sc_weight,
+                                                                     loss_function.mag_weight, loss_function.wave_l1)
+            res = pit(enhance, target, return_comb)
         if not return_comb:
             return res
         return res[0], [(i, j) for j, i in enumerate(res[1].cpu().tolist())]
@@ -582,6 +597,231 @@ class MRSTFTLoss(torch.nn.Module):
         if self.wave_l1 > 0.0:
             loss = loss + self.wave_l1 * l1_loss(enhanced, sources)
         return loss
+
+    def extra_repr(self):
+        return f"resolutions={self.resolutions}, sc_weight={self.sc_weight}, mag_weight={self.mag_weight}, wave_l1={self.wave_l1}"
+
+
+# ---- the permutation-invariant multi-resolution STFT loss (the sehip_mrl_pair_* kernels of csrc/mrstft_loss.hip) ------------------------
+_pit_mrstft_workspaces = {}   # (B, S, C, n, resolutions, device) -> PitMRSTFTWorkspace of the functional form; a PitMRSTFTLoss owns its own
+
+
+def _pit_mrstft_view(shape):
+    """(B, S, C, n) of enhance / target [B, S, ..., n]: the last axis is a row's samples, the axes between are its channels"""
+    c = 1
+    for d in shape[2:-1]:
+        c *= int(d)
+    return int(shape[0]), int(shape[1]), c, int(shape[-1])
+
+
+def _pit_mrstft_shape_check(shape, what):
+    if len(shape) < 3:
+        raise SehipError(f"{what}: expected [batch, speakers, ..., samples], got {tuple(shape)}")
+    if not 1 <= int(shape[1]) <= PIT_MAX_SPEAKERS:
+        raise SehipError(f"{what}: S={int(shape[1])} speakers outside [1, {PIT_MAX_SPEAKERS}] in {tuple(shape)}")
+    if any(int(d) == 0 for d in shape):
+        raise SehipError(f"{what}: empty input of shape {tuple(shape)}")
+
+
+class PitMRSTFTWorkspace:
+    """Every buffer of one pit_mrstft_loss call on enhance / target of `shape` [B, S, ..., n]: the windows, the per-workgroup sums of all
+    resolutions ((2 S S + S) floats per workgroup), the pair terms, the pair matrix, the permutation, the loss, the backward factors per
+    (resolution, target), the frame-gradient scratch of the B S C estimated rows at the largest resolution and the small buffers of the
+    waveform-L1 pair matrix.  `generation` counts the forward passes: a backward pass whose forward is no longer the latest one on these
+    buffers is refused instead of differentiating the wrong call."""
+
+    def __init__(self, shape, resolutions, device):
+        from ._lib import lib
+        _pit_mrstft_shape_check(shape, "pit_mrstft_loss")
+        b, s, c, n = self.view = _pit_mrstft_view(shape)
+        self.res_host = ops.mrl_check(resolutions, b * c, n, "pit_mrstft_loss")    # refusals first: nothing is allocated for a bad shape
+        self.resolutions = tuple(tuple(r) for r in self.res_host.tolist())
+        f32 = dict(device=device, dtype=torch.float32)
+        i32 = dict(device=device, dtype=torch.int32)
+        R = len(self.resolutions)
+        self.windows = [ops.mrl_window(nf, w, device) for nf, _, w in self.resolutions]
+        self.floats = [lib().sehip_mrl_pair_blocks(b, s, c, n, h) for _, h, _ in self.resolutions]
+        self.offsets = [sum(self.floats[:r]) for r in range(R)]
+        self.partials = torch.empty(sum(self.floats), **f32)
+        self.terms = torch.empty(R, s, s, 2, **f32)
+        self.matrix = torch.empty(s, s, **f32)
+        self.perm = torch.empty(s, **i32)
+        self.loss = torch.empty((), **f32)
+        self.stats = torch.empty(R, s, 2, **f32)
+        self.fgrad = torch.empty(max(b * s * c * lib().sehip_mrl_frames(n, h) * w for _, h, w in self.resolutions), **f32)
+        self.l1_partials = torch.empty(ops.pit_pointwise_blocks(b, s, c, n), s * s, **f32)
+        self.l1_pairs = torch.empty(s, s, **f32)
+        self.l1_perm = torch.empty(s, **i32)
+        self.l1_loss = torch.empty(1, **f32)
+        self.generation = 0
+
+    def nbytes(self):
+        own = [self.partials, self.terms, self.matrix, self.perm, self.loss, self.stats, self.fgrad, self.l1_partials, self.l1_pairs,
+               self.l1_perm, self.l1_loss]
+        return sum(t.numel() * t.element_size() for t in own + self.windows)
+
+
+def _pit_mrstft_check(enhance, target, what="pit_mrstft_loss"):
+    """every refusal that needs no workspace, before anything is allocated or launched"""
+    from ._lib import require_gpu
+    if not torch.is_tensor(enhance) or not torch.is_tensor(target):
+        raise SehipError(f"{what}: needs device tensors")
+    require_gpu(enhance, what)
+    require_gpu(target, what)
+    if enhance.shape != target.shape:
+        raise ValueError(f"{what}: shapes differ: {tuple(enhance.shape)} vs {tuple(target.shape)}")
+    _pit_mrstft_shape_check(enhance.shape, what)
+
+
+def _pit_mrstft_key(shape, resolutions, device):
+    from . import metric
+    return _pit_mrstft_view(shape) + (tuple(tuple(int(v) for v in r) for r in resolutions), str(metric._device(device)))
+
+
+def pit_mrstft_workspace(shape, resolutions=MRSTFT_RESOLUTIONS, device="cuda"):
+    """The cached workspace of the functional pit_mrstft_loss / pit_mrstft_terms for inputs of `shape` [B, S, ..., n].  The loss fetches it
+    itself; a caller that records the loss into a hipGraph calls this BEFORE the capture begins, so that the recording allocates nothing
+    but the call's results."""
+    _pit_mrstft_shape_check(shape, "pit_mrstft_loss")
+    key = _pit_mrstft_key(shape, resolutions, device)
+    ws = _pit_mrstft_workspaces.get(key)
+    if ws is None:
+        ws = PitMRSTFTWorkspace(shape, resolutions, device)
+        if not torch.cuda.is_current_stream_capturing():
+            _pit_mrstft_workspaces[key] = ws   # (a buffer born inside a capture lives in that graph's pool: it serves that recording only)
+    return ws
+
+
+def _pit_mrstft_forward(e, r, ws, sc_weight, mag_weight, wave_l1):
+    """the forward launches on [B, S, C, n] fp32: the waveform-L1 pair matrix if it is asked for, one launch per resolution and the
+    select; results stay in ws.loss / ws.perm / ws.matrix / ws.terms / ws.stats"""
+    from ._lib import call, ptr, stream
+    st = stream()
+    b, s, c, n = ws.view
+    extra = None
+    if wave_l1 > 0.0:
+        call("sehip_pit_pointwise_fwd", ptr(e), ptr(r), b, s, c, n, 0, ptr(ws.l1_partials), ptr(ws.l1_pairs), ptr(ws.l1_perm),
+             ptr(ws.l1_loss), st)
+        extra = ws.l1_pairs
+    for (nf, hop, win), window, off in zip(ws.resolutions, ws.windows, ws.offsets):
+        call("sehip_mrl_pair_forward", ptr(e), ptr(r), b, s, c, n, nf, hop, win, ptr(window), ptr(ws.partials[off:]), st)
+    call("sehip_mrl_pair_select", ptr(ws.partials), len(ws.resolutions), ptr(ws.res_host), b, s, c, n, float(sc_weight), float(mag_weight),
+         ptr(extra), float(wave_l1), ptr(ws.terms), ptr(ws.matrix), ptr(ws.perm), ptr(ws.loss), ptr(ws.stats), st)
+    ws.generation += 1
+
+
+MRSTFT_GATHER_ROWS = 65535    # MRL_MAX_ROWS of csrc/mrstft_loss.hip: the rows one sehip_mrl_gather launch takes
+
+
+class _PitMRSTFTLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, est, ref, ws, sc_weight, mag_weight, wave_l1):
+        e = est.detach().reshape(ws.view).contiguous().float()
+        r = ref.detach().reshape(ws.view).contiguous().float()
+        _pit_mrstft_forward(e, r, ws, sc_weight, mag_weight, wave_l1)
+        ctx.ws, ctx.weights, ctx.generation, ctx.shape = ws, (float(sc_weight), float(mag_weight), float(wave_l1)), ws.generation, est.shape
+        ctx.save_for_backward(e, r)
+        perm = ws.perm.clone()
+        ctx.mark_non_differentiable(perm)
+        return ws.loss.clone(), perm
+
+    @staticmethod
+    def backward(ctx, g, _gp):
+        from ._lib import call, lib, ptr, stream
+        ws = ctx.ws
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None, None
+        if ws.generation != ctx.generation:
+            raise SehipError("pit_mrstft_loss: another forward pass ran on this workspace before this one's backward pass; give each loss "
+                             "that is live at the same time a PitMRSTFTLoss module of its own")
+        e, r = ctx.saved_tensors
+        g = g.reshape(1).contiguous().float()
+        st = stream()
+        b, s, c, n = ws.view
+        scw, magw, wave_l1 = ctx.weights
+        R = len(ws.resolutions)
+        rows = b * s * c
+        grad = torch.empty(rows, n, device=g.device, dtype=torch.float32)
+        if wave_l1 > 0.0:      # d (wave_l1 / S) sum_j mean |enhance[:, perm[j]] - target[:, j]|, written; the resolutions add to it
+            gl = g * wave_l1
+            call("sehip_pit_pointwise_bwd", ptr(e), ptr(r), ptr(ws.perm), ptr(gl), b, s, c, n, 0, ptr(grad), st)
+        for i, ((nf, hop, win), window) in enumerate(zip(ws.resolutions, ws.windows)):
+            call("sehip_mrl_pair_backward", ptr(e), ptr(r), b, s, c, n, nf, hop, win, ptr(window), ptr(ws.stats[i]), ptr(ws.perm), ptr(g),
+                 scw / R / s, magw / R / s, ptr(ws.fgrad), st)
+            per_row = lib().sehip_mrl_frames(n, hop) * win
+            for r0 in range(0, rows, MRSTFT_GATHER_ROWS):
+                call("sehip_mrl_gather", ptr(ws.fgrad[r0 * per_row:]), min(MRSTFT_GATHER_ROWS, rows - r0), n, nf, hop, win,
+                     int(i > 0 or wave_l1 > 0.0), ptr(grad[r0:]), st)
+        return grad.view(ctx.shape), None, None, None, None, None
+
+
+def pit_mrstft_loss(enhance, target, resolutions=MRSTFT_RESOLUTIONS, sc_weight=1.0, mag_weight=1.0, wave_l1=0.0, return_comb=False, ws=None):
+    """The multi-resolution STFT loss under batch-level permutation-invariant training (src/loss.py:58-100, as pit_loss_pointwise and
+    pit_loss_sisdr have it) of device tensors enhance / target [B, S, ..., n], speakers on axis 1, 1 <= S <= 6 -> 0-dim float32 device
+    tensor, differentiable with respect to `enhance` (csrc/mrstft_loss.hip).  For estimated speaker i and target speaker j
+
+        M[i, j] = (1 / R) sum_r (sc_weight sc + mag_weight mag)(enhance[:, i], target[:, j]) + wave_l1 mean |enhance[:, i] - target[:, j]|
+
+    with (sc, mag) the terms of mrstft_loss, norms and mean over the B C rows of the pair; perm is the first minimum of
+    sum_j M[perm[j], j] over itertools.permutations(range(S)) (strict '<' from 1e9, the sum in fp32 over j ascending) and the loss is
+    (1 / S) sum_j M[perm[j], j].  With return_comb the device tensor perm [S] int32 (perm[j] = the estimate matched with target j) is
+    returned as well.  No gradient flows through the choice, `target` gets none, and the conventions of mrstft_loss carry over.
+
+    Every signal is transformed once per resolution -- 2 S transforms per row group fill the S x S matrix -- and the permutation is
+    picked and read on the device: no readback and no atomics, every sum in a fixed order, so two runs give the same bits and forward +
+    backward can be captured into one graph (pit_mrstft_workspace(...) before the capture).  After the first call at a shape nothing but
+    the results is allocated.  The pair terms carry the bits of mrstft_terms(enhance[:, i], target[:, j]).
+
+    Refused before any allocation or launch: shapes that differ (ValueError), fewer than 3 axes, more than 6 speakers, and whatever
+    mrstft_loss refuses for B C rows of n samples (SehipError).  As with mrstft_loss all calls at one shape share one workspace, so only
+    the LATEST forward pass at a shape can be differentiated; give each loss that is live at the same time a PitMRSTFTLoss of its own
+    (or pass `ws`, a PitMRSTFTWorkspace of the caller's own)."""
+    _pit_mrstft_check(enhance, target)
+    if ws is None:
+        ws = pit_mrstft_workspace(enhance.shape, resolutions, enhance.device)
+    loss, perm = _PitMRSTFTLoss.apply(enhance, target, ws, float(sc_weight), float(mag_weight), float(wave_l1))
+    return (loss, perm) if return_comb else loss
+
+
+def pit_mrstft_terms(enhance, target, resolutions=MRSTFT_RESOLUTIONS, sc_weight=1.0, mag_weight=1.0, wave_l1=0.0, ws=None):
+    """(terms [R, S, S, 2], the pair matrix M [S, S], perm [S] int32) on the device, from the forward launches of pit_mrstft_loss:
+    terms[r, i, j] = (sc, mag) of resolution r for (enhance[:, i], target[:, j]).  Not differentiable."""
+    _pit_mrstft_check(enhance, target, "pit_mrstft_terms")
+    if ws is None:
+        ws = pit_mrstft_workspace(enhance.shape, resolutions, enhance.device)
+    e = enhance.detach().reshape(ws.view).contiguous().float()
+    r = target.detach().reshape(ws.view).contiguous().float()
+    _pit_mrstft_forward(e, r, ws, float(sc_weight), float(mag_weight), float(wave_l1))
+    return ws.terms.clone(), ws.matrix.clone(), ws.perm.clone()
+
+
+class PitMRSTFTLoss(torch.nn.Module):
+    """pit_mrstft_loss(enhance, target, resolutions, sc_weight, mag_weight, wave_l1) as a module that owns its buffers: one workspace per
+    input shape, kept for the life of the module (a captured graph refers to them), so feed it a bounded set of shapes.  wave_l1 > 0
+    adds wave_l1 * mean |enhance[:, i] - target[:, j]| to every pair before the permutation is picked ('pit-l1+mrstft': the Demucs
+    denoiser recipe for separation networks)."""
+
+    def __init__(self, resolutions=MRSTFT_RESOLUTIONS, sc_weight=1.0, mag_weight=1.0, wave_l1=0.0):
+        super().__init__()
+        self.resolutions = tuple(tuple(int(v) for v in r) for r in resolutions)
+        self.sc_weight, self.mag_weight, self.wave_l1 = float(sc_weight), float(mag_weight), float(wave_l1)
+        self._workspaces = {}
+
+    def workspace(self, shape, device):
+        """this module's buffers for inputs of `shape` on `device`; call it before a capture that records the loss"""
+        _pit_mrstft_shape_check(shape, "pit_mrstft_loss")
+        key = _pit_mrstft_key(shape, self.resolutions, device)
+        ws = self._workspaces.get(key)
+        if ws is None:
+            ws = PitMRSTFTWorkspace(shape, self.resolutions, device)
+            if not torch.cuda.is_current_stream_capturing():
+                self._workspaces[key] = ws
+        return ws
+
+    def forward(self, enhance, target, return_comb=False):
+        _pit_mrstft_check(enhance, target)       # (before the workspace: a refusal allocates nothing)
+        return pit_mrstft_loss(enhance, target, self.resolutions, self.sc_weight, self.mag_weight, self.wave_l1, return_comb,
+                               self.workspace(enhance.shape, enhance.device))
 
     def extra_repr(self):
         return f"resolutions={self.resolutions}, sc_weight={self.sc_weight}, mag_weight={self.mag_weight}, wave_l1={self.wave_l1}"

@@ -122,7 +122,20 @@ class Solver(object):
                                  "(an STFT-domain model): train it with l1, mse or psa")
             if _cfg(config.optim, "pit_apply", False):
                 raise SehipError(f"optim.loss '{config.optim.loss}' with optim.pit_apply is not built: the permutation-invariant losses "
-                                 "are si-sdr, l1 and mse")
+                                 f"are si-sdr, l1 and mse, and optim.loss 'pit-{config.optim.loss}' ('pit-mrstft' / 'pit-l1+mrstft'), "
+                                 "which is permutation-invariant by itself")
+        if _cfg(getattr(config, "optim", None), "loss", None) in ("pit-mrstft", "pit-l1+mrstft"):
+            # the permutation-invariant multi-resolution STFT loss: waveforms [batch, speakers, ...], and no second PIT around it
+            if config.model.name in STFT_MODELS:
+                raise SehipError(f"optim.loss '{config.optim.loss}' is taken on waveforms; model '{config.model.name}' returns spectra "
+                                 "(an STFT-domain model): train it with l1, mse or psa")
+            if config.model.name not in MULTI_SPEECH_SEPERATION_MODELS:
+                raise SehipError(f"optim.loss '{config.optim.loss}' matches estimated with target speakers; model '{config.model.name}' "
+                                 f"does not return [batch, speakers, ...] (those are {sorted(MULTI_SPEECH_SEPERATION_MODELS)}): train "
+                                 f"it with '{config.optim.loss[4:]}'")
+            if _cfg(config.optim, "pit_apply", False):
+                raise SehipError(f"optim.loss '{config.optim.loss}' is permutation-invariant by itself: with optim.pit_apply the "
+                                 "permutation would be searched twice; drop optim.pit_apply")
         self.train_dataloader = train_dataloader
         self.validation_dataloader = validation_dataloader
         self.test_dataloader = test_dataloader
