@@ -22,6 +22,8 @@
 //               and picks the permutation, and frames<1> with the row pairing read from that permutation.
 // Conventions of the gradient: a cell the forward clamped (P < 1e-7) passes nothing; |.| at exactly 0 has derivative 0; ||Y - X|| = 0
 // gives an exactly zero sc gradient.
+#include <type_traits>   // std::integral_constant (mrl_dispatch)
+
 #include "fft512.h"      // fft_detail::cossin_frac, the compile-time series behind g_fft_tw
 #include "pit_perm.h"    // PIT_MAXS, pit_best_permutation
 
@@ -398,19 +400,25 @@ int mrl_check(const char* who, int rows, long n, int n_fft, int hop, int win) {
     return 0;
 }
 
-// one instantiation per transform size
+// The one dispatch from n_fft to LG = log2(n_fft), a kernel's template argument: f is called with std::integral_constant<int, LG>, so
+// every launch of this file has one instantiation per transform size (mrl_check has run: n_fft is a power of two in [64, 2048]).
+template <class F>
+auto mrl_dispatch(int n_fft, F&& f) {
+    switch (n_fft) {
+        case 64: return f(std::integral_constant<int, 6>{});
+        case 128: return f(std::integral_constant<int, 7>{});
+        case 256: return f(std::integral_constant<int, 8>{});
+        case 512: return f(std::integral_constant<int, 9>{});
+        case 1024: return f(std::integral_constant<int, 10>{});
+        default: return f(std::integral_constant<int, 11>{});      // 2048
+    }
+}
+
 template <int MODE>
 void mrl_launch(const MrlFrames& a, int rows, hipStream_t st) {
     const dim3 grid((a.T + 1) / 2, rows);
     const size_t lds = (size_t)(MODE == 2 ? 2 : 3) * a.n_fft * sizeof(float2) + (MODE == 0 ? 16 * sizeof(float) : 0);
-    switch (a.n_fft) {
-        case 64: mrl_frames_kernel<MODE, 6><<<grid, MRL_THREADS, lds, st>>>(a); break;
-        case 128: mrl_frames_kernel<MODE, 7><<<grid, MRL_THREADS, lds, st>>>(a); break;
-        case 256: mrl_frames_kernel<MODE, 8><<<grid, MRL_THREADS, lds, st>>>(a); break;
-        case 512: mrl_frames_kernel<MODE, 9><<<grid, MRL_THREADS, lds, st>>>(a); break;
-        case 1024: mrl_frames_kernel<MODE, 10><<<grid, MRL_THREADS, lds, st>>>(a); break;
-        default: mrl_frames_kernel<MODE, 11><<<grid, MRL_THREADS, lds, st>>>(a); break;      // 2048 (mrl_check has run)
-    }
+    mrl_dispatch(a.n_fft, [&](auto lg) { mrl_frames_kernel<MODE, decltype(lg)::value><<<grid, MRL_THREADS, lds, st>>>(a); });
 }
 
 MrlFrames mrl_args(const float* enh, const float* src, const float* window, long n, int n_fft, int hop, int win) {
@@ -633,10 +641,15 @@ __global__ __launch_bounds__(MRL_THREADS) void mrl_pair_bwd_kernel(MrlFrames a, 
     mrl_frames_body<1, LG>(a, (b * S + i) * C + c, (b * S + j) * C + c, a.stats + 2 * j);
 }
 
-int mrl_pair_check(const char* who, int B, int S, int C, long n, int n_fft, int hop, int win) {
+int mrl_pair_rows_check(const char* who, int B, int S, int C) {
     SEHIP_REQUIRE(S >= 1 && S <= PIT_MAXS, "%s: S=%d speakers outside [1, %d]", who, S, PIT_MAXS);
     SEHIP_REQUIRE(B >= 1 && C >= 1 && (long)B * C <= MRL_MAX_ROWS, "%s: rows=%ld (B=%d times C=%d) outside [1, %d]", who, (long)B * C, B, C,
                   MRL_MAX_ROWS);
+    return 0;
+}
+
+int mrl_pair_check(const char* who, int B, int S, int C, long n, int n_fft, int hop, int win) {
+    if (int e = mrl_pair_rows_check(who, B, S, C)) return e;
     return mrl_check(who, B * C, n, n_fft, hop, win);
 }
 
@@ -762,16 +775,7 @@ extern "C" int sehip_mrl_pair_forward(const float* enh, const float* src, int B,
     a.nblk = (long)grid.x * grid.y;
     const size_t lds = mrl_pair_lds(S, n_fft);
     hipStream_t st = (hipStream_t)stream;
-    int e = 0;
-    switch (n_fft) {
-        case 64: e = mrl_pair_launch_fwd<6>(a, grid, lds, st); break;
-        case 128: e = mrl_pair_launch_fwd<7>(a, grid, lds, st); break;
-        case 256: e = mrl_pair_launch_fwd<8>(a, grid, lds, st); break;
-        case 512: e = mrl_pair_launch_fwd<9>(a, grid, lds, st); break;
-        case 1024: e = mrl_pair_launch_fwd<10>(a, grid, lds, st); break;
-        default: e = mrl_pair_launch_fwd<11>(a, grid, lds, st); break;      // 2048 (mrl_check has run)
-    }
-    if (e) return e;
+    if (int e = mrl_dispatch(n_fft, [&](auto lg) { return mrl_pair_launch_fwd<decltype(lg)::value>(a, grid, lds, st); })) return e;
     SEHIP_CHECK_LAUNCH("mrl_pair_forward");
     sehip_note_kernel("mrl_pair_forward n_fft=%d T=%d S=%d lds=%zu", n_fft, a.f.T, S, lds);
     return 0;
@@ -780,9 +784,7 @@ extern "C" int sehip_mrl_pair_forward(const float* enh, const float* src, int B,
 extern "C" int sehip_mrl_pair_select(const float* partials, int n_res, const int* res, int B, int S, int C, long n, float sc_weight,
                                      float mag_weight, const float* extra, float extra_weight, float* terms, float* matrix, int* perm,
                                      float* loss, float* stats, void* stream) {
-    SEHIP_REQUIRE(S >= 1 && S <= PIT_MAXS, "mrl_pair_select: S=%d speakers outside [1, %d]", S, PIT_MAXS);
-    SEHIP_REQUIRE(B >= 1 && C >= 1 && (long)B * C <= MRL_MAX_ROWS, "mrl_pair_select: rows=%ld (B=%d times C=%d) outside [1, %d]",
-                  (long)B * C, B, C, MRL_MAX_ROWS);
+    if (int e = mrl_pair_rows_check("mrl_pair_select", B, S, C)) return e;
     if (int e = sehip_mrl_check(n_res, res, B * C, n)) return e;
     SEHIP_REQUIRE(partials && terms && matrix && perm && loss && stats, "mrl_pair_select: null pointer");
     MrlPairFinal f{};
@@ -819,14 +821,7 @@ extern "C" int sehip_mrl_pair_backward(const float* enh, const float* src, int B
     const dim3 grid((a.T + 1) / 2, B * C, S);
     const size_t lds = (size_t)3 * n_fft * sizeof(float2);
     hipStream_t st = (hipStream_t)stream;
-    switch (n_fft) {
-        case 64: mrl_pair_bwd_kernel<6><<<grid, MRL_THREADS, lds, st>>>(a, perm, S, C); break;
-        case 128: mrl_pair_bwd_kernel<7><<<grid, MRL_THREADS, lds, st>>>(a, perm, S, C); break;
-        case 256: mrl_pair_bwd_kernel<8><<<grid, MRL_THREADS, lds, st>>>(a, perm, S, C); break;
-        case 512: mrl_pair_bwd_kernel<9><<<grid, MRL_THREADS, lds, st>>>(a, perm, S, C); break;
-        case 1024: mrl_pair_bwd_kernel<10><<<grid, MRL_THREADS, lds, st>>>(a, perm, S, C); break;
-        default: mrl_pair_bwd_kernel<11><<<grid, MRL_THREADS, lds, st>>>(a, perm, S, C); break;
-    }
+    mrl_dispatch(n_fft, [&](auto lg) { mrl_pair_bwd_kernel<decltype(lg)::value><<<grid, MRL_THREADS, lds, st>>>(a, perm, S, C); });
     SEHIP_CHECK_LAUNCH("mrl_pair_backward");
     sehip_note_kernel("mrl_pair_backward n_fft=%d T=%d S=%d", n_fft, a.T, S);
     return 0;

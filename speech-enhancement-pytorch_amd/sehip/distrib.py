@@ -66,13 +66,12 @@ def get_loss_function(config, device="gpu"):
         return loss_phase_sensitive_spectral_approximation
     if config.loss in ("stoi", "estoi"):      # negated STOI / ESTOI of the waveforms; the Solver sets the sample rate (Solver._sample_rate)
         return StoiLoss(extended=config.loss == "estoi")
-    if config.loss in ("mrstft", "l1+mrstft"):    # multi-resolution STFT loss of the waveforms, with the waveform L1 for 'l1+mrstft'
+    if config.loss in ("mrstft", "l1+mrstft", "pit-mrstft", "pit-l1+mrstft"):
+        # multi-resolution STFT loss of the waveforms, with the waveform L1 for 'l1+'; 'pit-': the same under batch-level PIT, for models
+        # that return [batch, speakers, ...]
         res = getattr(config, "mrstft_resolutions", None)
-        return MRSTFTLoss(MRSTFT_RESOLUTIONS if res is None else [tuple(r) for r in res], wave_l1=1.0 if config.loss == "l1+mrstft" else 0.0)
-    if config.loss in ("pit-mrstft", "pit-l1+mrstft"):    # the same under batch-level PIT, for models that return [batch, speakers, ...]
-        res = getattr(config, "mrstft_resolutions", None)
-        return PitMRSTFTLoss(MRSTFT_RESOLUTIONS if res is None else [tuple(r) for r in res],
-                             wave_l1=1.0 if config.loss == "pit-l1+mrstft" else 0.0)
+        return (PitMRSTFTLoss if config.loss.startswith("pit-") else MRSTFTLoss)(
+            MRSTFT_RESOLUTIONS if res is None else [tuple(r) for r in res], wave_l1=1.0 if "l1+" in config.loss else 0.0)
     raise ValueError(f"Loss function {config.loss} cannot use...")
 
 

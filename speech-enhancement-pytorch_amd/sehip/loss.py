@@ -2,7 +2,8 @@
 torch.nn.functional in the reference, src/distrib.py:263-275)."""
 import torch
 
-from . import ops
+from . import _lib, ops
+from ._cache import CaptureAwareCache, canonical_device
 from ._lib import SehipError
 
 
@@ -72,17 +73,18 @@ def pit_loss_sisdr(enhance, target, return_comb=False):
 PIT_POINTWISE_MAX_ROWS = 1 << 20      # PITPW_MAXROWS of csrc/loss.hip: B * C, the pair-matrix kernel's grid extent
 
 
-def _pit_pointwise_view(shape):
+def _pit_pointwise_view(shape, fold_above=PIT_POINTWISE_MAX_ROWS):
     """(B, S, C, n) the pair-matrix kernel sees for enhance / target [B, S, ..., n]: the last axis is a row's samples and the axes
     between are its rows.  A tensor with more rows than the kernel's grid takes (an STFT-domain estimate [B, S, C, F, T, 2] at the
     shipped size has B C F T rows of 2 samples) is ONE row per (batch, speaker) instead: the terms are element-wise and every
-    pair loss is a batch mean, so the grouping changes no value, only which shapes are taken."""
+    pair loss is a batch mean, so the grouping changes no value, only which shapes are taken.  fold_above=None keeps the rows as
+    they are (pit_mrstft_loss: a row is a signal with transforms of its own)."""
     b, s = int(shape[0]), int(shape[1])
     n = int(shape[-1]) if len(shape) >= 3 else 1
     c = 1
     for d in shape[2:-1]:
         c *= int(d)
-    if b * c > PIT_POINTWISE_MAX_ROWS:
+    if fold_above is not None and b * c > fold_above:
         c, n = 1, c * n
     return b, s, c, n
 
@@ -107,25 +109,21 @@ class _PitPointwiseLoss(torch.autograd.Function):
 
 
 PIT_MAX_SPEAKERS = 6      # PIT_MAXS of csrc/loss.hip
-_pit_workspaces = {}      # (device, B, S, C, n) -> partials [blocks, S*S]: scratch of the pair-matrix kernel, consumed by the select kernel
-                          # of the same call on the same stream, so one buffer per shape serves every call (and exists before a capture)
+_pit_workspaces = CaptureAwareCache()     # (device, B, S, C, n) -> partials [blocks, S*S]: scratch of the pair-matrix kernel, consumed by
+                                          # the select kernel of the same call on the same stream, so one buffer per shape serves every call
+
+
+def _pit_pointwise_partials(device, b, s, c, n):
+    return torch.empty(ops.pit_pointwise_blocks(b, s, c, n), s * s, device=device, dtype=torch.float32)
 
 
 def pit_pointwise_workspace(shape, device):
     """The cached pair-matrix workspace for enhance / target of `shape` [B, S, ..., n] on `device`.  pit_loss_pointwise fetches it
     itself; a caller that records the loss into a hipGraph calls this BEFORE the capture begins, so the recording allocates nothing
     but the call's own outputs."""
-    device = torch.device(device)
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    b, s, c, n = _pit_pointwise_view(shape)
-    key = (device, b, s, c, n)
-    ws = _pit_workspaces.get(key)
-    if ws is None:
-        ws = torch.empty(ops.pit_pointwise_blocks(b, s, c, n), s * s, device=device, dtype=torch.float32)
-        if not (device.type == "cuda" and torch.cuda.is_current_stream_capturing()):
-            _pit_workspaces[key] = ws      # (a buffer born inside a capture lives in that graph's pool: it serves that recording only)
-    return ws
+    device = canonical_device(device)
+    view = _pit_pointwise_view(shape)
+    return _pit_workspaces.get((device,) + view, _pit_pointwise_partials, device, *view)
 
 
 def pit_loss_pointwise(enhance, target, mode, return_comb=False):
@@ -142,8 +140,7 @@ def pit_loss_pointwise(enhance, target, mode, return_comb=False):
         raise SehipError(f"enhance and target shape did not match...{tuple(enhance.shape)}, {tuple(target.shape)}")
     if enhance.dim() < 2 or not 1 <= enhance.shape[1] <= PIT_MAX_SPEAKERS:
         raise SehipError(f"pit_loss_pointwise: expected [batch, speakers <= {PIT_MAX_SPEAKERS}, ...], got {tuple(enhance.shape)}")
-    from ._lib import require_gpu
-    require_gpu(enhance, "pit_loss_pointwise")
+    _lib.require_gpu(enhance, "pit_loss_pointwise")
     loss, perm, _ = _PitPointwiseLoss.apply(enhance, target, mode, pit_pointwise_workspace(enhance.shape, enhance.device))
     return (loss, perm) if return_comb else loss
 
@@ -170,11 +167,7 @@ def pit_loss(enhance, target, loss_function, return_comb=False):
         if loss_function is mrstft_loss:
             res = pit_mrstft_loss(enhance, target, return_comb=return_comb)
         else:
-            pit = loss_function.__dict__.get("_pit")
-            if pit is None:                        # (through __dict__: a helper of this call path, not a registered submodule)
-                pit = loss_function.__dict__["_pit"] = PitMRSTFTLoss(loss_function.resolutions, loss_function.sc_weight,
-                                                                     loss_function.mag_weight, loss_function.wave_l1)
-            res = pit(enhance, target, return_comb)
+            res = loss_function.pit()(enhance, target, return_comb)
         if not return_comb:
             return res
         return res[0], [(i, j) for j, i in enumerate(res[1].cpu().tolist())]
@@ -262,15 +255,82 @@ def loss_phase_sensitive_spectral_approximation(enhance, target, mixture):
     return _PsaLoss.apply(enhance, target, mixture)
 
 
+# ---- what the losses with a workspace share: stoi_loss, mrstft_loss, pit_mrstft_loss and their modules ---------------------------------
+def _rows_of(shape):
+    """the rows of [..., n]: the product of every axis but the last"""
+    rows = 1
+    for s in shape[:-1]:
+        rows *= int(s)
+    return rows
+
+
+def _as_rows(x, view):
+    """x as the contiguous fp32 rows the kernels read, cut from the autograd graph (the loss's own backward pass carries the gradient)"""
+    return x.detach().reshape(view).contiguous().float()
+
+
+def _check_pair(enhanced, sources, what, shape_check=None):
+    """every refusal that needs no workspace, before anything is allocated or launched; shape_check(shape, what) stands in for the
+    refusal of an empty input where a loss asks more of the shape"""
+    if not torch.is_tensor(enhanced) or not torch.is_tensor(sources):
+        raise SehipError(f"{what}: needs device tensors")
+    _lib.require_gpu(enhanced, what)
+    _lib.require_gpu(sources, what)
+    if enhanced.shape != sources.shape:
+        raise ValueError(f"{what}: shapes differ: {tuple(enhanced.shape)} vs {tuple(sources.shape)}")
+    if shape_check is not None:
+        shape_check(enhanced.shape, what)
+    elif enhanced.dim() < 1 or enhanced.numel() == 0:
+        raise SehipError(f"{what}: empty input of shape {tuple(enhanced.shape)}")
+
+
+class _LossWorkspace:
+    """The base of the three workspaces.  `generation` counts the forward passes on these buffers: a backward pass whose forward is no
+    longer the latest one is refused instead of differentiating the wrong call.  A subclass lists its buffers in tensors()."""
+    generation = 0
+
+    def forward_ran(self):
+        self.generation += 1
+        return self.generation
+
+    def refuse_stale(self, generation, loss, module):
+        """`generation` is what forward_ran() gave the forward pass that is about to be differentiated; `module` is the module to
+        recommend, with its article ('an MRSTFTLoss')"""
+        if self.generation != generation:
+            raise SehipError(f"{loss}: another forward pass ran on this workspace before this one's backward pass; give each loss that "
+                             f"is live at the same time {module} module of its own")
+
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for t in self.tensors())
+
+
+class _WorkspaceLoss(torch.nn.Module):
+    """The base of the three modules that own their buffers: one workspace per input shape, kept for the life of the module (a captured
+    graph refers to them).  A subclass gives WHAT (the name in its refusals), SHAPE_CHECK, _key(shape, device), _make(shape, device) and
+    _loss(enhanced, sources, ws, *extra); its forward() is _run() under the subclass's own signature."""
+    SHAPE_CHECK = None
+
+    def __init__(self):
+        super().__init__()
+        self._workspaces = CaptureAwareCache()
+
+    def workspace(self, shape, device):
+        """this module's buffers for inputs of `shape` on `device`; call it before a capture that records the loss"""
+        return self._workspaces.get(self._key(shape, device), self._make, shape, device)
+
+    def _run(self, enhanced, sources, *extra):
+        _check_pair(enhanced, sources, self.WHAT, self.SHAPE_CHECK)      # (before the workspace: a refusal allocates nothing)
+        return self._loss(enhanced, sources, self.workspace(enhanced.shape, enhanced.device), *extra)
+
+
 # ---- STOI / ESTOI as a loss (csrc/stoi_loss.hip behind the forward launches of csrc/stoi.hip) ------------------------------------------
-_stoi_loss_workspaces = {}    # (rows, n, sr, extended, device) -> StoiLossWorkspace of the functional form; a StoiLoss module owns its own
+_stoi_loss_workspaces = CaptureAwareCache()    # (rows, n, sr, extended, device) -> StoiLossWorkspace of the functional form
 
 
-class StoiLossWorkspace:
+class StoiLossWorkspace(_LossWorkspace):
     """Every buffer of one stoi_loss call on `rows` pairs of n samples at sr, forward and backward: the forward's (as
     sehip.metric.stoi_workspace, but never shared with the metric, so a STOI() call between a forward and its backward changes nothing)
-    plus the value pair and the backward's scratch.  `generation` counts the forward passes: a backward pass whose forward is no longer
-    the latest one on these buffers is refused instead of differentiating the wrong call."""
+    plus the value pair and the backward's scratch."""
 
     def __init__(self, rows, n, sr, device):
         from . import metric
@@ -288,51 +348,28 @@ class StoiLossWorkspace:
         self.fgrad = torch.empty(rows, spectra, metric.STOI_FRAME, **f32)
         self.inv = torch.empty(rows, self.frames, device=self.kept.device, dtype=torch.int32)
         self.g10 = None if self.sig is None else torch.empty(rows, self.n10, **f32)
-        self.generation = 0
 
-
-def _stoi_loss_check(enhanced, sources, what="stoi_loss"):
-    """the metric's refusals, before anything is allocated or launched"""
-    from ._lib import require_gpu
-    if not torch.is_tensor(enhanced) or not torch.is_tensor(sources):
-        raise SehipError(f"{what}: needs device tensors")
-    require_gpu(enhanced, what)
-    require_gpu(sources, what)
-    if enhanced.shape != sources.shape:
-        raise ValueError(f"{what}: shapes differ: {tuple(enhanced.shape)} vs {tuple(sources.shape)}")
-    if enhanced.dim() < 1 or enhanced.numel() == 0:
-        raise SehipError(f"{what}: empty input of shape {tuple(enhanced.shape)}")
+    def tensors(self):
+        own = [self.d, self.mean, self.seg, self.dtob, self.fgrad, self.inv, self.level, self.kept, self.src, self.tob] + self.partial
+        return own + ([] if self.sig is None else [self.sig, self.g10])       # (the resampling table is metric.stoi_resample_table's)
 
 
 def stoi_loss_workspace(shape, sr=16000, extended=False, device="cuda"):
     """The cached workspace of the functional stoi_loss / stoi_loss_rows for inputs of `shape` [..., T].  The loss fetches it itself; a
     caller that records the loss into a hipGraph calls this BEFORE the capture begins, so that the recording allocates nothing but
     the call's results."""
-    from . import metric
-    n = int(shape[-1])
-    rows = 1
-    for s in shape[:-1]:
-        rows *= int(s)
-    key = (rows, n, int(sr), bool(extended), str(metric._device(device)))
-    ws = _stoi_loss_workspaces.get(key)
-    if ws is None:
-        ws = StoiLossWorkspace(rows, n, sr, device)
-        if not torch.cuda.is_current_stream_capturing():
-            _stoi_loss_workspaces[key] = ws    # (a buffer born inside a capture lives in that graph's pool: it serves that recording only)
-    return ws
+    rows, n = _rows_of(shape), int(shape[-1])
+    return _stoi_loss_workspaces.get((rows, n, int(sr), bool(extended), canonical_device(device)), StoiLossWorkspace, rows, n, sr, device)
 
 
 class _StoiLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, est, ref, ws, extended, per_row):
         from . import metric
-        rows, n = ws.rows, ws.n
-        e = est.detach().reshape(rows, n).contiguous().float()
-        r = ref.detach().reshape(rows, n).contiguous().float()
+        e, r = _as_rows(est, (ws.rows, ws.n)), _as_rows(ref, (ws.rows, ws.n))
         ext = int(bool(extended))
         metric.stoi_forward(r, e, ws.fwd, ext, ws.d, ws.mean)
-        ws.generation += 1
-        ctx.ws, ctx.ext, ctx.per_row, ctx.generation, ctx.shape = ws, ext, per_row, ws.generation, est.shape
+        ctx.ws, ctx.ext, ctx.per_row, ctx.generation, ctx.shape = ws, ext, per_row, ws.forward_ran(), est.shape
         ctx.save_for_backward(*([e] if ws.sig is None else []))   # off 10 kHz the backward pass reads the resampled estimate the forward left
         return torch.neg(ws.d if per_row else ws.mean)
 
@@ -342,9 +379,7 @@ class _StoiLoss(torch.autograd.Function):
         ws = ctx.ws
         if not ctx.needs_input_grad[0]:
             return None, None, None, None, None
-        if ws.generation != ctx.generation:
-            raise SehipError("stoi_loss: another forward pass ran on this workspace before this one's backward pass; give each loss that "
-                             "is live at the same time a StoiLoss module of its own")
+        ws.refuse_stale(ctx.generation, "stoi_loss", "a StoiLoss")
         rows, n, n10, frames = ws.rows, ws.n, ws.n10, ws.frames
         g = g.reshape(rows if ctx.per_row else 1).contiguous().float()
         st = stream()
@@ -361,11 +396,9 @@ class _StoiLoss(torch.autograd.Function):
         return grad.view(ctx.shape), None, None, None, None
 
 
-def _stoi_loss(enhanced, sources, sr, extended, per_row, ws=None):
-    _stoi_loss_check(enhanced, sources)
-    if ws is None:
-        ws = stoi_loss_workspace(enhanced.shape, sr, extended, enhanced.device)
-    return _StoiLoss.apply(enhanced, sources, ws, bool(extended), per_row)
+def _stoi_loss(enhanced, sources, sr, extended, per_row):
+    _check_pair(enhanced, sources, "stoi_loss")
+    return _StoiLoss.apply(enhanced, sources, stoi_loss_workspace(enhanced.shape, sr, extended, enhanced.device), bool(extended), per_row)
 
 
 def stoi_loss(enhanced, sources, sr=16000, extended=False):
@@ -391,33 +424,26 @@ def stoi_loss_rows(enhanced, sources, sr=16000, extended=False):
     return _stoi_loss(enhanced, sources, sr, extended, True)
 
 
-class StoiLoss(torch.nn.Module):
+class StoiLoss(_WorkspaceLoss):
     """stoi_loss(enhanced, sources, sr, extended) as a module that owns its buffers: one workspace per input shape, kept for the life of
     the module (a captured graph refers to them), so feed it a bounded set of shapes -- training segments, not clips of every length."""
+    WHAT = "stoi_loss"
 
     def __init__(self, sr=16000, extended=False):
         super().__init__()
         self.sr, self.extended = int(sr), bool(extended)
-        self._workspaces = {}
 
-    def workspace(self, shape, device):
-        """this module's buffers for inputs of `shape` on `device`; call it before a capture that records the loss"""
-        from . import metric
-        key = (tuple(shape), self.sr, str(metric._device(device)))
-        ws = self._workspaces.get(key)
-        if ws is None:
-            n = int(shape[-1])
-            rows = 1
-            for s in shape[:-1]:
-                rows *= int(s)
-            ws = StoiLossWorkspace(rows, n, self.sr, device)
-            if not torch.cuda.is_current_stream_capturing():
-                self._workspaces[key] = ws
-        return ws
+    def _key(self, shape, device):
+        return (tuple(shape), self.sr, canonical_device(device))
+
+    def _make(self, shape, device):
+        return StoiLossWorkspace(_rows_of(shape), int(shape[-1]), self.sr, device)
+
+    def _loss(self, enhanced, sources, ws):
+        return _StoiLoss.apply(enhanced, sources, ws, self.extended, False)
 
     def forward(self, enhanced, sources):
-        _stoi_loss_check(enhanced, sources)      # (before the workspace: a refusal allocates nothing)
-        return _stoi_loss(enhanced, sources, self.sr, self.extended, False, self.workspace(enhanced.shape, enhanced.device))
+        return self._run(enhanced, sources)
 
     def extra_repr(self):
         return f"sr={self.sr}, extended={self.extended}"
@@ -425,21 +451,13 @@ class StoiLoss(torch.nn.Module):
 
 # ---- the multi-resolution STFT loss (csrc/mrstft_loss.hip) -----------------------------------------------------------------------------
 MRSTFT_RESOLUTIONS = ((1024, 120, 600), (2048, 240, 1200), (512, 50, 240))     # (n_fft, hop, win_length)
-_mrstft_workspaces = {}       # (rows, n, resolutions, device) -> MRSTFTWorkspace of the functional form; an MRSTFTLoss module owns its own
+_mrstft_workspaces = CaptureAwareCache()       # (rows, n, resolutions, device) -> MRSTFTWorkspace of the functional form
 
 
-def _rows_of(shape):
-    rows = 1
-    for s in shape[:-1]:
-        rows *= int(s)
-    return rows
-
-
-class MRSTFTWorkspace:
+class MRSTFTWorkspace(_LossWorkspace):
     """Every buffer of one mrstft_loss call on `rows` pairs of n samples: the windows, the per-workgroup partial sums of all resolutions,
     the (sc, mag) terms, the loss, the two backward factors per resolution and the frame-gradient scratch (sized for the largest
-    resolution; the resolutions run one after another on one stream).  `generation` counts the forward passes: a backward pass whose
-    forward is no longer the latest one on these buffers is refused instead of differentiating the wrong call."""
+    resolution; the resolutions run one after another on one stream)."""
 
     def __init__(self, rows, n, resolutions, device):
         from ._lib import lib
@@ -456,27 +474,13 @@ class MRSTFTWorkspace:
         self.stats = torch.empty(len(self.resolutions), 2, **f32)
         self.loss = torch.empty((), **f32)
         self.fgrad = torch.empty(max(rows * lib().sehip_mrl_frames(n, h) * w for _, h, w in self.resolutions), **f32)
-        self.generation = 0
 
-    def nbytes(self):
-        return sum(t.numel() * t.element_size() for t in [self.partials, self.terms, self.stats, self.loss, self.fgrad] + self.windows)
-
-
-def _mrstft_check(enhanced, sources, what="mrstft_loss"):
-    from ._lib import require_gpu
-    if not torch.is_tensor(enhanced) or not torch.is_tensor(sources):
-        raise SehipError(f"{what}: needs device tensors")
-    require_gpu(enhanced, what)
-    require_gpu(sources, what)
-    if enhanced.shape != sources.shape:
-        raise ValueError(f"{what}: shapes differ: {tuple(enhanced.shape)} vs {tuple(sources.shape)}")
-    if enhanced.dim() < 1 or enhanced.numel() == 0:
-        raise SehipError(f"{what}: empty input of shape {tuple(enhanced.shape)}")
+    def tensors(self):
+        return [self.partials, self.terms, self.stats, self.loss, self.fgrad] + self.windows
 
 
 def _mrstft_key(shape, resolutions, device):
-    from . import metric
-    return (_rows_of(shape), int(shape[-1]), tuple(tuple(int(v) for v in r) for r in resolutions), str(metric._device(device)))
+    return (_rows_of(shape), int(shape[-1]), tuple(tuple(int(v) for v in r) for r in resolutions), canonical_device(device))
 
 
 def mrstft_loss_workspace(shape, resolutions=MRSTFT_RESOLUTIONS, device="cuda"):
@@ -484,32 +488,27 @@ def mrstft_loss_workspace(shape, resolutions=MRSTFT_RESOLUTIONS, device="cuda"):
     caller that records the loss into a hipGraph calls this BEFORE the capture begins, so that the recording allocates nothing but
     the call's results."""
     key = _mrstft_key(shape, resolutions, device)
-    ws = _mrstft_workspaces.get(key)
-    if ws is None:
-        ws = MRSTFTWorkspace(key[0], key[1], resolutions, device)
-        if not torch.cuda.is_current_stream_capturing():
-            _mrstft_workspaces[key] = ws       # (a buffer born inside a capture lives in that graph's pool: it serves that recording only)
-    return ws
+    return _mrstft_workspaces.get(key, MRSTFTWorkspace, key[0], key[1], resolutions, device)
 
 
-def _mrstft_forward(e, r, ws, sc_weight, mag_weight):
-    """the forward launches on rows [rows, n] fp32: one per resolution and the finalize; results stay in ws.loss / ws.terms / ws.stats"""
+def _mrstft_forward(enhanced, sources, ws, sc_weight, mag_weight):
+    """the forward launches on the rows [rows, n] fp32 of both signals (returned): one per resolution and the finalize; results stay in
+    ws.loss / ws.terms / ws.stats"""
     from ._lib import call, ptr, stream
+    e, r = _as_rows(enhanced, (ws.rows, ws.n)), _as_rows(sources, (ws.rows, ws.n))
     st = stream()
     for (nf, hop, win), window, off in zip(ws.resolutions, ws.windows, ws.offsets):
         call("sehip_mrl_forward", ptr(e), ptr(r), ws.rows, ws.n, nf, hop, win, ptr(window), ptr(ws.partials[off:]), st)
     call("sehip_mrl_finalize", ptr(ws.partials), len(ws.resolutions), ptr(ws.res_host), ws.rows, ws.n, float(sc_weight), float(mag_weight),
          ptr(ws.stats), ptr(ws.terms), ptr(ws.loss), st)
-    ws.generation += 1
+    return e, r, ws.forward_ran()
 
 
 class _MRSTFTLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, est, ref, ws, sc_weight, mag_weight):
-        e = est.detach().reshape(ws.rows, ws.n).contiguous().float()
-        r = ref.detach().reshape(ws.rows, ws.n).contiguous().float()
-        _mrstft_forward(e, r, ws, sc_weight, mag_weight)
-        ctx.ws, ctx.weights, ctx.generation, ctx.shape = ws, (float(sc_weight), float(mag_weight)), ws.generation, est.shape
+        e, r, ctx.generation = _mrstft_forward(est, ref, ws, sc_weight, mag_weight)
+        ctx.ws, ctx.weights, ctx.shape = ws, (float(sc_weight), float(mag_weight)), est.shape
         ctx.save_for_backward(e, r)
         return ws.loss.clone()
 
@@ -519,9 +518,7 @@ class _MRSTFTLoss(torch.autograd.Function):
         ws = ctx.ws
         if not ctx.needs_input_grad[0]:
             return None, None, None, None, None
-        if ws.generation != ctx.generation:
-            raise SehipError("mrstft_loss: another forward pass ran on this workspace before this one's backward pass; give each loss that "
-                             "is live at the same time an MRSTFTLoss module of its own")
+        ws.refuse_stale(ctx.generation, "mrstft_loss", "an MRSTFTLoss")
         e, r = ctx.saved_tensors
         g = g.reshape(1).contiguous().float()
         st = stream()
@@ -553,7 +550,7 @@ def mrstft_loss(enhanced, sources, resolutions=MRSTFT_RESOLUTIONS, sc_weight=1.0
     at a shape can be differentiated; the backward pass of an earlier one raises SehipError.  Give each loss that is live at the same
     time an MRSTFTLoss module of its own (or pass `ws`, an MRSTFTWorkspace of the caller's own).  Workspaces stay allocated (a captured graph refers to their buffers): one per shape, each
     with the frame-gradient scratch of win_length floats per frame and row of the largest resolution."""
-    _mrstft_check(enhanced, sources)
+    _check_pair(enhanced, sources, "mrstft_loss")
     if ws is None:
         ws = mrstft_loss_workspace(enhanced.shape, resolutions, enhanced.device)
     return _MRSTFTLoss.apply(enhanced, sources, ws, float(sc_weight), float(mag_weight))
@@ -561,57 +558,57 @@ def mrstft_loss(enhanced, sources, resolutions=MRSTFT_RESOLUTIONS, sc_weight=1.0
 
 def mrstft_terms(enhanced, sources, resolutions=MRSTFT_RESOLUTIONS, ws=None):
     """[R, 2] float32 on the device: (sc, mag) of each resolution, from the forward launches of mrstft_loss.  Not differentiable."""
-    _mrstft_check(enhanced, sources, "mrstft_terms")
+    _check_pair(enhanced, sources, "mrstft_terms")
     if ws is None:
         ws = mrstft_loss_workspace(enhanced.shape, resolutions, enhanced.device)
-    e = enhanced.detach().reshape(ws.rows, ws.n).contiguous().float()
-    r = sources.detach().reshape(ws.rows, ws.n).contiguous().float()
-    _mrstft_forward(e, r, ws, 1.0, 1.0)
+    _mrstft_forward(enhanced, sources, ws, 1.0, 1.0)
     return ws.terms.clone()
 
 
-class MRSTFTLoss(torch.nn.Module):
-    """mrstft_loss(enhanced, sources, resolutions, sc_weight, mag_weight) as a module that owns its buffers: one workspace per input
-    shape, kept for the life of the module (a captured graph refers to them), so feed it a bounded set of shapes.  wave_l1 > 0 adds
-    wave_l1 * l1_loss(enhanced, sources), the waveform term of the Demucs denoiser recipe."""
+class _MRSTFTModule(_WorkspaceLoss):
+    """what MRSTFTLoss and PitMRSTFTLoss share: the settings and how they print"""
 
     def __init__(self, resolutions=MRSTFT_RESOLUTIONS, sc_weight=1.0, mag_weight=1.0, wave_l1=0.0):
         super().__init__()
         self.resolutions = tuple(tuple(int(v) for v in r) for r in resolutions)
         self.sc_weight, self.mag_weight, self.wave_l1 = float(sc_weight), float(mag_weight), float(wave_l1)
-        self._workspaces = {}
-
-    def workspace(self, shape, device):
-        """this module's buffers for inputs of `shape` on `device`; call it before a capture that records the loss"""
-        key = _mrstft_key(shape, self.resolutions, device)
-        ws = self._workspaces.get(key)
-        if ws is None:
-            ws = MRSTFTWorkspace(key[0], key[1], self.resolutions, device)
-            if not torch.cuda.is_current_stream_capturing():
-                self._workspaces[key] = ws
-        return ws
-
-    def forward(self, enhanced, sources):
-        _mrstft_check(enhanced, sources)         # (before the workspace: a refusal allocates nothing)
-        loss = mrstft_loss(enhanced, sources, self.resolutions, self.sc_weight, self.mag_weight, self.workspace(enhanced.shape, enhanced.device))
-        if self.wave_l1 > 0.0:
-            loss = loss + self.wave_l1 * l1_loss(enhanced, sources)
-        return loss
 
     def extra_repr(self):
         return f"resolutions={self.resolutions}, sc_weight={self.sc_weight}, mag_weight={self.mag_weight}, wave_l1={self.wave_l1}"
 
 
+class MRSTFTLoss(_MRSTFTModule):
+    """mrstft_loss(enhanced, sources, resolutions, sc_weight, mag_weight) as a module that owns its buffers: one workspace per input
+    shape, kept for the life of the module (a captured graph refers to them), so feed it a bounded set of shapes.  wave_l1 > 0 adds
+    wave_l1 * l1_loss(enhanced, sources), the waveform term of the Demucs denoiser recipe."""
+    WHAT = "mrstft_loss"
+
+    def _key(self, shape, device):
+        return _mrstft_key(shape, self.resolutions, device)
+
+    def _make(self, shape, device):
+        return MRSTFTWorkspace(_rows_of(shape), int(shape[-1]), self.resolutions, device)
+
+    def _loss(self, enhanced, sources, ws):
+        loss = _MRSTFTLoss.apply(enhanced, sources, ws, self.sc_weight, self.mag_weight)
+        if self.wave_l1 > 0.0:
+            loss = loss + self.wave_l1 * l1_loss(enhanced, sources)
+        return loss
+
+    def forward(self, enhanced, sources):
+        return self._run(enhanced, sources)
+
+    def pit(self):
+        """this loss under permutation-invariant training, with its settings and workspaces of its own: pit_loss's helper, built on first
+        use and kept through __dict__, so it is no registered submodule and state_dict() is unchanged"""
+        pit = self.__dict__.get("_pit")
+        if pit is None:
+            pit = self.__dict__["_pit"] = PitMRSTFTLoss(self.resolutions, self.sc_weight, self.mag_weight, self.wave_l1)
+        return pit
+
+
 # ---- the permutation-invariant multi-resolution STFT loss (the sehip_mrl_pair_* kernels of csrc/mrstft_loss.hip) ------------------------
-_pit_mrstft_workspaces = {}   # (B, S, C, n, resolutions, device) -> PitMRSTFTWorkspace of the functional form; a PitMRSTFTLoss owns its own
-
-
-def _pit_mrstft_view(shape):
-    """(B, S, C, n) of enhance / target [B, S, ..., n]: the last axis is a row's samples, the axes between are its channels"""
-    c = 1
-    for d in shape[2:-1]:
-        c *= int(d)
-    return int(shape[0]), int(shape[1]), c, int(shape[-1])
+_pit_mrstft_workspaces = CaptureAwareCache()   # (B, S, C, n, resolutions, device) -> PitMRSTFTWorkspace of the functional form
 
 
 def _pit_mrstft_shape_check(shape, what):
@@ -623,17 +620,16 @@ def _pit_mrstft_shape_check(shape, what):
         raise SehipError(f"{what}: empty input of shape {tuple(shape)}")
 
 
-class PitMRSTFTWorkspace:
+class PitMRSTFTWorkspace(_LossWorkspace):
     """Every buffer of one pit_mrstft_loss call on enhance / target of `shape` [B, S, ..., n]: the windows, the per-workgroup sums of all
     resolutions ((2 S S + S) floats per workgroup), the pair terms, the pair matrix, the permutation, the loss, the backward factors per
     (resolution, target), the frame-gradient scratch of the B S C estimated rows at the largest resolution and the small buffers of the
-    waveform-L1 pair matrix.  `generation` counts the forward passes: a backward pass whose forward is no longer the latest one on these
-    buffers is refused instead of differentiating the wrong call."""
+    waveform-L1 pair matrix."""
 
     def __init__(self, shape, resolutions, device):
         from ._lib import lib
         _pit_mrstft_shape_check(shape, "pit_mrstft_loss")
-        b, s, c, n = self.view = _pit_mrstft_view(shape)
+        b, s, c, n = self.view = _pit_pointwise_view(shape, None)
         self.res_host = ops.mrl_check(resolutions, b * c, n, "pit_mrstft_loss")    # refusals first: nothing is allocated for a bad shape
         self.resolutions = tuple(tuple(r) for r in self.res_host.tolist())
         f32 = dict(device=device, dtype=torch.float32)
@@ -653,49 +649,33 @@ class PitMRSTFTWorkspace:
         self.l1_pairs = torch.empty(s, s, **f32)
         self.l1_perm = torch.empty(s, **i32)
         self.l1_loss = torch.empty(1, **f32)
-        self.generation = 0
 
-    def nbytes(self):
-        own = [self.partials, self.terms, self.matrix, self.perm, self.loss, self.stats, self.fgrad, self.l1_partials, self.l1_pairs,
-               self.l1_perm, self.l1_loss]
-        return sum(t.numel() * t.element_size() for t in own + self.windows)
+    def tensors(self):
+        return [self.partials, self.terms, self.matrix, self.perm, self.loss, self.stats, self.fgrad, self.l1_partials, self.l1_pairs,
+                self.l1_perm, self.l1_loss] + self.windows
 
 
 def _pit_mrstft_check(enhance, target, what="pit_mrstft_loss"):
-    """every refusal that needs no workspace, before anything is allocated or launched"""
-    from ._lib import require_gpu
-    if not torch.is_tensor(enhance) or not torch.is_tensor(target):
-        raise SehipError(f"{what}: needs device tensors")
-    require_gpu(enhance, what)
-    require_gpu(target, what)
-    if enhance.shape != target.shape:
-        raise ValueError(f"{what}: shapes differ: {tuple(enhance.shape)} vs {tuple(target.shape)}")
-    _pit_mrstft_shape_check(enhance.shape, what)
+    _check_pair(enhance, target, what, _pit_mrstft_shape_check)
 
 
 def _pit_mrstft_key(shape, resolutions, device):
-    from . import metric
-    return _pit_mrstft_view(shape) + (tuple(tuple(int(v) for v in r) for r in resolutions), str(metric._device(device)))
+    _pit_mrstft_shape_check(shape, "pit_mrstft_loss")      # (workspace(...) is public: the view below needs [batch, speakers, ..., samples])
+    return _pit_pointwise_view(shape, None) + (tuple(tuple(int(v) for v in r) for r in resolutions), canonical_device(device))
 
 
 def pit_mrstft_workspace(shape, resolutions=MRSTFT_RESOLUTIONS, device="cuda"):
     """The cached workspace of the functional pit_mrstft_loss / pit_mrstft_terms for inputs of `shape` [B, S, ..., n].  The loss fetches it
     itself; a caller that records the loss into a hipGraph calls this BEFORE the capture begins, so that the recording allocates nothing
     but the call's results."""
-    _pit_mrstft_shape_check(shape, "pit_mrstft_loss")
-    key = _pit_mrstft_key(shape, resolutions, device)
-    ws = _pit_mrstft_workspaces.get(key)
-    if ws is None:
-        ws = PitMRSTFTWorkspace(shape, resolutions, device)
-        if not torch.cuda.is_current_stream_capturing():
-            _pit_mrstft_workspaces[key] = ws   # (a buffer born inside a capture lives in that graph's pool: it serves that recording only)
-    return ws
+    return _pit_mrstft_workspaces.get(_pit_mrstft_key(shape, resolutions, device), PitMRSTFTWorkspace, shape, resolutions, device)
 
 
-def _pit_mrstft_forward(e, r, ws, sc_weight, mag_weight, wave_l1):
-    """the forward launches on [B, S, C, n] fp32: the waveform-L1 pair matrix if it is asked for, one launch per resolution and the
-    select; results stay in ws.loss / ws.perm / ws.matrix / ws.terms / ws.stats"""
+def _pit_mrstft_forward(enhance, target, ws, sc_weight, mag_weight, wave_l1):
+    """the forward launches on both signals as [B, S, C, n] fp32 (returned): the waveform-L1 pair matrix if it is asked for, one launch
+    per resolution and the select; results stay in ws.loss / ws.perm / ws.matrix / ws.terms / ws.stats"""
     from ._lib import call, ptr, stream
+    e, r = _as_rows(enhance, ws.view), _as_rows(target, ws.view)
     st = stream()
     b, s, c, n = ws.view
     extra = None
@@ -707,7 +687,7 @@ def _pit_mrstft_forward(e, r, ws, sc_weight, mag_weight, wave_l1):
         call("sehip_mrl_pair_forward", ptr(e), ptr(r), b, s, c, n, nf, hop, win, ptr(window), ptr(ws.partials[off:]), st)
     call("sehip_mrl_pair_select", ptr(ws.partials), len(ws.resolutions), ptr(ws.res_host), b, s, c, n, float(sc_weight), float(mag_weight),
          ptr(extra), float(wave_l1), ptr(ws.terms), ptr(ws.matrix), ptr(ws.perm), ptr(ws.loss), ptr(ws.stats), st)
-    ws.generation += 1
+    return e, r, ws.forward_ran()
 
 
 MRSTFT_GATHER_ROWS = 65535    # MRL_MAX_ROWS of csrc/mrstft_loss.hip: the rows one sehip_mrl_gather launch takes
@@ -716,10 +696,8 @@ MRSTFT_GATHER_ROWS = 65535    # MRL_MAX_ROWS of csrc/mrstft_loss.hip: the rows o
 class _PitMRSTFTLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, est, ref, ws, sc_weight, mag_weight, wave_l1):
-        e = est.detach().reshape(ws.view).contiguous().float()
-        r = ref.detach().reshape(ws.view).contiguous().float()
-        _pit_mrstft_forward(e, r, ws, sc_weight, mag_weight, wave_l1)
-        ctx.ws, ctx.weights, ctx.generation, ctx.shape = ws, (float(sc_weight), float(mag_weight), float(wave_l1)), ws.generation, est.shape
+        e, r, ctx.generation = _pit_mrstft_forward(est, ref, ws, sc_weight, mag_weight, wave_l1)
+        ctx.ws, ctx.weights, ctx.shape = ws, (float(sc_weight), float(mag_weight), float(wave_l1)), est.shape
         ctx.save_for_backward(e, r)
         perm = ws.perm.clone()
         ctx.mark_non_differentiable(perm)
@@ -731,9 +709,7 @@ class _PitMRSTFTLoss(torch.autograd.Function):
         ws = ctx.ws
         if not ctx.needs_input_grad[0]:
             return None, None, None, None, None, None
-        if ws.generation != ctx.generation:
-            raise SehipError("pit_mrstft_loss: another forward pass ran on this workspace before this one's backward pass; give each loss "
-                             "that is live at the same time a PitMRSTFTLoss module of its own")
+        ws.refuse_stale(ctx.generation, "pit_mrstft_loss", "a PitMRSTFTLoss")
         e, r = ctx.saved_tensors
         g = g.reshape(1).contiguous().float()
         st = stream()
@@ -789,39 +765,26 @@ def pit_mrstft_terms(enhance, target, resolutions=MRSTFT_RESOLUTIONS, sc_weight=
     _pit_mrstft_check(enhance, target, "pit_mrstft_terms")
     if ws is None:
         ws = pit_mrstft_workspace(enhance.shape, resolutions, enhance.device)
-    e = enhance.detach().reshape(ws.view).contiguous().float()
-    r = target.detach().reshape(ws.view).contiguous().float()
-    _pit_mrstft_forward(e, r, ws, float(sc_weight), float(mag_weight), float(wave_l1))
+    _pit_mrstft_forward(enhance, target, ws, float(sc_weight), float(mag_weight), float(wave_l1))
     return ws.terms.clone(), ws.matrix.clone(), ws.perm.clone()
 
 
-class PitMRSTFTLoss(torch.nn.Module):
+class PitMRSTFTLoss(_MRSTFTModule):
     """pit_mrstft_loss(enhance, target, resolutions, sc_weight, mag_weight, wave_l1) as a module that owns its buffers: one workspace per
     input shape, kept for the life of the module (a captured graph refers to them), so feed it a bounded set of shapes.  wave_l1 > 0
     adds wave_l1 * mean |enhance[:, i] - target[:, j]| to every pair before the permutation is picked ('pit-l1+mrstft': the Demucs
     denoiser recipe for separation networks)."""
+    WHAT, SHAPE_CHECK = "pit_mrstft_loss", staticmethod(_pit_mrstft_shape_check)
 
-    def __init__(self, resolutions=MRSTFT_RESOLUTIONS, sc_weight=1.0, mag_weight=1.0, wave_l1=0.0):
-        super().__init__()
-        self.resolutions = tuple(tuple(int(v) for v in r) for r in resolutions)
-        self.sc_weight, self.mag_weight, self.wave_l1 = float(sc_weight), float(mag_weight), float(wave_l1)
-        self._workspaces = {}
+    def _key(self, shape, device):
+        return _pit_mrstft_key(shape, self.resolutions, device)
 
-    def workspace(self, shape, device):
-        """this module's buffers for inputs of `shape` on `device`; call it before a capture that records the loss"""
-        _pit_mrstft_shape_check(shape, "pit_mrstft_loss")
-        key = _pit_mrstft_key(shape, self.resolutions, device)
-        ws = self._workspaces.get(key)
-        if ws is None:
-            ws = PitMRSTFTWorkspace(shape, self.resolutions, device)
-            if not torch.cuda.is_current_stream_capturing():
-                self._workspaces[key] = ws
-        return ws
+    def _make(self, shape, device):
+        return PitMRSTFTWorkspace(shape, self.resolutions, device)
+
+    def _loss(self, enhance, target, ws, return_comb):
+        loss, perm = _PitMRSTFTLoss.apply(enhance, target, ws, self.sc_weight, self.mag_weight, self.wave_l1)
+        return (loss, perm) if return_comb else loss
 
     def forward(self, enhance, target, return_comb=False):
-        _pit_mrstft_check(enhance, target)       # (before the workspace: a refusal allocates nothing)
-        return pit_mrstft_loss(enhance, target, self.resolutions, self.sc_weight, self.mag_weight, self.wave_l1, return_comb,
-                               self.workspace(enhance.shape, enhance.device))
-
-    def extra_repr(self):
-        return f"resolutions={self.resolutions}, sc_weight={self.sc_weight}, mag_weight={self.mag_weight}, wave_l1={self.wave_l1}"
+        return self._run(enhance, target, return_comb)

@@ -10,6 +10,7 @@ from math import gcd
 import numpy as np
 import torch
 
+from ._cache import CaptureAwareCache, canonical_device
 from ._lib import SehipError, call, lib, ptr, require_gpu, stream
 
 
@@ -34,18 +35,8 @@ def SI_SDR(reference, estimation, sr=16000):
 # ---- STOI ---------------------------------------------------------------------------------------------------------------------------
 STOI_FS, STOI_FRAME, STOI_BANDS = 10000, 256, 15
 STOI_MAX_P, STOI_MAX_Q, STOI_MAX_ROWS = 128, 1024, 32767
-
-
-def _device(device):
-    """torch.device with the index spelled out, so that 'cuda' and 'cuda:0' name one cache entry"""
-    device = torch.device(device)
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    return device
-
-
 _stoi_tables = {}        # (p, q, device) -> (table [p][2 L / p + 1], p, q, L)
-_stoi_workspaces = {}    # (rows, n, sr, device) -> dict of buffers
+_stoi_workspaces = CaptureAwareCache()    # (rows, n, sr, device) -> dict of buffers
 
 
 def stoi_ratio(sr, what="STOI"):
@@ -75,7 +66,7 @@ def stoi_resample_table(sr, device="cpu"):
     p, q = stoi_ratio(sr)
     if p == q:
         raise SehipError("STOI: 10 kHz input needs no resampling table")
-    device = _device(device)
+    device = canonical_device(device)
     key = (p, q, str(device))
     hit = _stoi_tables.get(key)
     if hit is not None:
@@ -102,7 +93,7 @@ def stoi_resample_table(sr, device="cpu"):
 def stoi_buffers(rows, n, sr, device, what="STOI"):
     """Fresh buffers of the forward launches on `rows` pairs of n samples at sr; every refusal names `what` (sehip.loss.stoi_loss keeps
     a set of its own, apart from the metric's cache)."""
-    device = _device(device)
+    device = canonical_device(device)
     p, q = stoi_ratio(sr, what)
     n10 = n if p == q else stoi_out_len(n, sr)
     if n10 < STOI_FRAME:
@@ -125,12 +116,8 @@ def stoi_buffers(rows, n, sr, device, what="STOI"):
 def stoi_workspace(rows, n, sr, device):
     """The buffers of one STOI call on `rows` pairs of n samples at sr, cached per (rows, n, sr, device): a call allocates nothing but its
     result, so it can be captured into a graph."""
-    device = _device(device)
-    key = (rows, n, int(sr), str(device))
-    ws = _stoi_workspaces.get(key)
-    if ws is None:
-        ws = _stoi_workspaces[key] = stoi_buffers(rows, n, sr, device)
-    return ws
+    device = canonical_device(device)
+    return _stoi_workspaces.get((rows, n, int(sr), device), stoi_buffers, rows, n, sr, device)
 
 
 def stoi_forward(r, e, ws, extended, d, out):

@@ -6,6 +6,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._cache import CaptureAwareCache, canonical_device
 from ._lib import call, ptr, stream, require_gpu
 
 BF16 = torch.bfloat16
@@ -230,25 +231,21 @@ def resample_frac(x, old_sr, new_sr):
     return out
 
 
-_mrl_windows = {}     # (n_fft, win_length, device) -> the periodic hann of win_length centred in n_fft zeros, fp32 [n_fft]
+_mrl_windows = CaptureAwareCache()     # (n_fft, win_length, device) -> the periodic hann of win_length centred in n_fft zeros, fp32 [n_fft]
+
+
+def _mrl_window_make(n_fft, win_length, device):
+    host = torch.zeros(n_fft, dtype=torch.float32)
+    lp = (n_fft - win_length) // 2
+    host[lp:lp + win_length] = torch.hann_window(win_length, periodic=True, dtype=torch.float64).float()
+    return host.to(device)
 
 
 def mrl_window(n_fft, win_length, device):
     """torch.stft's window for (n_fft, win_length): hann_window(win_length) (periodic, rounded once from float64) behind
     (n_fft - win_length) // 2 zeros, as a cached device table the kernels of csrc/mrstft_loss.hip read."""
-    device = torch.device(device)
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    key = (int(n_fft), int(win_length), str(device))
-    w = _mrl_windows.get(key)
-    if w is None:
-        host = torch.zeros(int(n_fft), dtype=torch.float32)
-        lp = (int(n_fft) - int(win_length)) // 2
-        host[lp:lp + int(win_length)] = torch.hann_window(int(win_length), periodic=True, dtype=torch.float64).float()
-        w = host.to(device)
-        if not (device.type == "cuda" and torch.cuda.is_current_stream_capturing()):
-            _mrl_windows[key] = w
-    return w
+    n_fft, win_length, device = int(n_fft), int(win_length), canonical_device(device)
+    return _mrl_windows.get((n_fft, win_length, device), _mrl_window_make, n_fft, win_length, device)
 
 
 def mrl_check(resolutions, rows, n, what="mrstft"):

@@ -59,6 +59,36 @@ def _cfg(obj, name, default):
     return getattr(obj, name, default)
 
 
+_NOT_BUILT = "optim.loss '{loss}' with optim.pit_apply is not built: the permutation-invariant losses are si-sdr, l1 and mse"
+_OWN_PIT = ", and optim.loss 'pit-{loss}' ('pit-mrstft' / 'pit-l1+mrstft'), which is permutation-invariant by itself"
+_PIT_TWICE = ("optim.loss '{loss}' is permutation-invariant by itself: with optim.pit_apply the permutation would be searched twice; drop "
+              "optim.pit_apply")
+# the optim.loss names that are taken on waveforms (the negated STOI / ESTOI, one row per (batch, speaker, channel); the multi-resolution
+# STFT loss, which takes its own transforms) -> (permutation-invariant by itself, so for [batch, speakers, ...] models only; the answer to
+# optim.pit_apply)
+_WAVEFORM_LOSSES = {"stoi": (False, _NOT_BUILT), "estoi": (False, _NOT_BUILT),
+                    "mrstft": (False, _NOT_BUILT + _OWN_PIT), "l1+mrstft": (False, _NOT_BUILT + _OWN_PIT),
+                    "pit-mrstft": (True, _PIT_TWICE), "pit-l1+mrstft": (True, _PIT_TWICE)}
+
+
+def _refuse_loss(config):
+    """the combinations of optim.loss, model and optim.pit_apply that cannot train, from the configuration alone: before any device is
+    touched"""
+    loss = _cfg(getattr(config, "optim", None), "loss", None)
+    if loss not in _WAVEFORM_LOSSES:
+        return
+    own_pit, pit_apply = _WAVEFORM_LOSSES[loss]
+    model = config.model.name
+    if model in STFT_MODELS:
+        raise SehipError(f"optim.loss '{loss}' is taken on waveforms; model '{model}' returns spectra (an STFT-domain model): train it "
+                         "with l1, mse or psa")
+    if own_pit and model not in MULTI_SPEECH_SEPERATION_MODELS:
+        raise SehipError(f"optim.loss '{loss}' matches estimated with target speakers; model '{model}' does not return "
+                         f"[batch, speakers, ...] (those are {sorted(MULTI_SPEECH_SEPERATION_MODELS)}): train it with '{loss[4:]}'")
+    if _cfg(config.optim, "pit_apply", False):
+        raise SehipError(pit_apply.format(loss=loss))
+
+
 class DevicePrefetcher:
     """Iterates a dataloader ONE batch ahead: the host -> HBM copies of batch k + 1 are enqueued on a stream of their own while step k
     computes, and the consumer's stream waits for them when it takes the batch (with a pinned-memory DataLoader the copies overlap
@@ -106,36 +136,7 @@ class DevicePrefetcher:
 class Solver(object):
     def __init__(self, config, model, optimizer=None, loss_function=None, train_dataloader=None,
                  validation_dataloader=None, test_dataloader=None, device="gpu", writer=None):
-        if _cfg(getattr(config, "optim", None), "loss", None) in ("stoi", "estoi"):
-            # the negated STOI / ESTOI is a loss on waveforms, one row per (batch, speaker, channel): refused from the configuration alone,
-            # before any device is touched
-            if config.model.name in STFT_MODELS:
-                raise SehipError(f"optim.loss '{config.optim.loss}' is taken on waveforms; model '{config.model.name}' returns spectra "
-                                 "(an STFT-domain model): train it with l1, mse or psa")
-            if _cfg(config.optim, "pit_apply", False):
-                raise SehipError(f"optim.loss '{config.optim.loss}' with optim.pit_apply is not built: the permutation-invariant losses "
-                                 "are si-sdr, l1 and mse")
-        if _cfg(getattr(config, "optim", None), "loss", None) in ("mrstft", "l1+mrstft"):
-            # the multi-resolution STFT loss takes its own transforms of waveforms: refused from the configuration alone as well
-            if config.model.name in STFT_MODELS:
-                raise SehipError(f"optim.loss '{config.optim.loss}' is taken on waveforms; model '{config.model.name}' returns spectra "
-                                 "(an STFT-domain model): train it with l1, mse or psa")
-            if _cfg(config.optim, "pit_apply", False):
-                raise SehipError(f"optim.loss '{config.optim.loss}' with optim.pit_apply is not built: the permutation-invariant losses "
-                                 f"are si-sdr, l1 and mse, and optim.loss 'pit-{config.optim.loss}' ('pit-mrstft' / 'pit-l1+mrstft'), "
-                                 "which is permutation-invariant by itself")
-        if _cfg(getattr(config, "optim", None), "loss", None) in ("pit-mrstft", "pit-l1+mrstft"):
-            # the permutation-invariant multi-resolution STFT loss: waveforms [batch, speakers, ...], and no second PIT around it
-            if config.model.name in STFT_MODELS:
-                raise SehipError(f"optim.loss '{config.optim.loss}' is taken on waveforms; model '{config.model.name}' returns spectra "
-                                 "(an STFT-domain model): train it with l1, mse or psa")
-            if config.model.name not in MULTI_SPEECH_SEPERATION_MODELS:
-                raise SehipError(f"optim.loss '{config.optim.loss}' matches estimated with target speakers; model '{config.model.name}' "
-                                 f"does not return [batch, speakers, ...] (those are {sorted(MULTI_SPEECH_SEPERATION_MODELS)}): train "
-                                 f"it with '{config.optim.loss[4:]}'")
-            if _cfg(config.optim, "pit_apply", False):
-                raise SehipError(f"optim.loss '{config.optim.loss}' is permutation-invariant by itself: with optim.pit_apply the "
-                                 "permutation would be searched twice; drop optim.pit_apply")
+        _refuse_loss(config)
         self.train_dataloader = train_dataloader
         self.validation_dataloader = validation_dataloader
         self.test_dataloader = test_dataloader
